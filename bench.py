@@ -34,6 +34,8 @@ BF16_MFMA_PEAK_TF = 2500.0  # MI355X_MICROARCH.md: bf16 MFMA dense peak (no spar
 PROF_STEPS = 2
 STRICT_STEPS = 3
 MFMAS_PER_PRODUCT = {"f32": 1, "bf16x3": 3, "bf16x6": 6, "f16x3": 3}
+DUMP_CAP_BYTES = 60 * 10**6   # --dump-outputs: at most this many bytes of .npy payload in all (64 MB with headers)
+DUMP_SEED = 0
 
 
 def parse():
@@ -65,9 +67,15 @@ def parse():
     ap.add_argument("--busy-json", default=os.path.join(ROOT, "profiles", "conv_mfma_busy.json"),
                     help="matrix-pipe counters of the conv kernels from a rocprofv3 --pmc pass (optional)")
     ap.add_argument("--dump-kernels", default=None, help="write the per-conv-shape timing table to this file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write rank 0's outputs of the last timed step (the accumulated flows F(k->0)) as DIR/flow_<k>_to_0.npy "
+                         "in float32; above %d MB in all, a fixed seeded sample of each array" % (DUMP_CAP_BYTES // 10**6))
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "lookup_traffic.json"),
                     help="per-launch HBM bytes of the lookup kernel from a rocprofv3 --pmc pass (optional)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def usable_cpus():
@@ -342,6 +350,8 @@ def main():
     outs = run_steps(a.steps)
     fence()
     elapsed = time.perf_counter() - t0
+    # host copy of the last timed step's outputs, taken before anything else runs on the model (outside the timed region)
+    outs_host = [o.detach().float().cpu() for o in outs] if (a.dump_outputs and rank == 0 and outs is not None) else None
     # Per-kernel HIP-event timing for the roofline objects: PROF_STEPS extra steps of the same workload right
     # after the timed region, with the pair groups on ONE stream - in the timed region two streams overlap
     # kernels, which makes a single kernel's event-to-event time meaningless.
@@ -608,6 +618,8 @@ def main():
                     f.write("%-44s launches/step %4d  ms/step %8.3f  TFLOP/s %7.2f\n" % (
                         k, d["launches"] // PROF_STEPS, d["total_ms"] / PROF_STEPS,
                         d["work"] / (d["total_ms"] * 1e-3) / 1e12))
+        if outs_host is not None:
+            res["dumped_outputs"] = dump_outputs(outs_host, a.dump_outputs)
         if not a.no_parity:
             res["parity"] = parity_vs_golden(outs, a)
         if strict is not None:
@@ -625,6 +637,29 @@ def main():
     if grouped:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(outs, out_dir):
+    """Write the accumulated flows [F(2->0), ..., F(n-1->0)] as out_dir/flow_<k>_to_0.npy (float32, full shape).  If they
+    exceed DUMP_CAP_BYTES in all, each array is replaced by the same fraction of its elements, flat indices drawn without
+    replacement by torch.randperm seeded with DUMP_SEED and sorted: the sample depends on the shapes only, so two builds
+    run with the same arguments write comparable files.  -> summary for the JSON line."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(o.numel() * 4 for o in outs)
+    frac = min(1.0, DUMP_CAP_BYTES / float(total)) if total else 1.0
+    files = {}
+    for k, o in enumerate(outs):
+        name = "flow_%d_to_0" % (k + 2)
+        arr = o.float().contiguous()
+        if frac < 1.0:
+            n = int(arr.numel() * frac)
+            idx = torch.randperm(arr.numel(), generator=torch.Generator().manual_seed(DUMP_SEED))[:n].sort().values
+            arr = arr.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), arr.numpy().astype(np.float32, copy=False))
+        files[name] = {"shape": list(o.shape), "saved_shape": list(arr.shape)}
+    return {"dir": out_dir, "dtype": "float32", "sampled": frac < 1.0, "sample_seed": DUMP_SEED if frac < 1.0 else None,
+            "files": files}
 
 
 def parity_vs_golden(outs, a):

@@ -104,7 +104,15 @@ def test_gma_attention_aggregate(golden, gma_sd):
     attn = O.gma_attention(inp, gma_sd)
     close(attn.sum(-1), g["attn_rowsum"], 1e-5, what="attention row sums")
     close(attn[:, 0, g["attn_rows_sel"]], g["attn_rows"], 1e-6, rtol=1e-3, what="attention rows")
-    close(O.gma_aggregate(attn, T(g["motion"]), gma_sd, "update_block.aggregator"), g["motion_global"], 1e-4,
+    # the reference's whole attention matrix (gma_c1_attn.npz: the weights above its floor, the rest are 0 here)
+    s = golden("gma_c1_attn")
+    ref_attn = np.zeros(int(np.prod(s["shape"])), np.float32)
+    ref_attn[s["index"]] = s["value"]
+    ref_attn = ref_attn.reshape(s["shape"])
+    close(attn, ref_attn, 1e-6, rtol=1e-3, what="attention")
+    # the aggregation on the reference's own attention: the logits are large enough that the last bit of the CPU GEMM
+    # (thread count, ISA) moves the weights by ~3e-4 relative, which the aggregate's 1e-4 would otherwise have to absorb
+    close(O.gma_aggregate(T(ref_attn), T(g["motion"]), gma_sd, "update_block.aggregator"), g["motion_global"], 1e-4,
           what="aggregate")
 
 

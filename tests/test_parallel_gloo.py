@@ -177,7 +177,9 @@ def _worker(rank, world, port, q):
                                   on_result=lambda k, o: got.append((k, o)))
     ok &= res == {} and got == [(k, 10 * k) for k in range(rank, nseq, world)] and 1 <= peak[0] <= 2 and not alive
     q.put((rank, bool(ok)))
-    dist.barrier()
+    # gloo's own barrier: dist.barrier() asks torch for the machine's accelerator first, which initialises the HIP runtime
+    # and opens the GPU in every one of these CPU-only ranks
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
