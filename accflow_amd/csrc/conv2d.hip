@@ -1010,13 +1010,14 @@ extern "C" int accflow_conv_stat_slots(const accflow_conv_desc* desc) {
 bool accflow_conv_stem_eligible(const accflow_conv_desc& d);              // conv_stem.hip
 int accflow_launch_conv_stem(const accflow_conv_desc& d, hipStream_t st);
 
-// (the pre-split GRU state rides on the tap-specialised 5-tap instantiations: both A/B switches of that route must be on)
-static bool accflow_conv_gru16_supported() {
+// (the pre-split GRU state rides on the tap-specialised 5-tap instantiations: both A/B switches of that route must be on;
+// read once per process - Python asks this function instead of re-reading the switches, so the two cannot disagree)
+extern "C" int accflow_conv_gru16_supported(void) {
   static const bool ok = [] {
     const char* a = getenv("ACCFLOW_DIRECT_KT"); const char* b = getenv("ACCFLOW_DIRECT_W4"); const char* c = getenv("ACCFLOW_S16M");
     return !(a && atoi(a) == 0) && !(b && atoi(b) == 0) && !(c && atoi(c) != 0);
   }();
-  return ok;
+  return ok ? 1 : 0;
 }
 
 extern "C" int accflow_conv2d_f32(const accflow_conv_desc* desc, void* stream) {

@@ -269,6 +269,12 @@ USE_S16 = os.environ.get("ACCFLOW_S16", "1") == "1"
 S16_VIA_MULTI = os.environ.get("ACCFLOW_S16_VIA_MULTI", "0") == "1"   # in0 / in1 S16 convs on the multi-source kernel (A/B)
 
 
+def conv_gru16_supported():
+    """The library's answer (its environment switches, read once per process): the GRU epilogues can run on the pre-split
+    state (accflow_conv_desc.e0_fmt / p32)."""
+    return bool(_lib.load().accflow_conv_gru16_supported())
+
+
 def s16_active():
     """True when the update block / encoders keep their conv-to-conv activations in the pre-split S16 format: the fp16
     split mode only (a guard retry in bf16x6 runs the fp32-activation path), ACCFLOW_S16=0 switches it off (A/B)."""

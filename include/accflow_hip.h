@@ -283,6 +283,10 @@ int accflow_conv2d_f32(const accflow_conv_desc* desc, void* stream);
 int accflow_conv_stat_slots(const accflow_conv_desc* desc);
 /* != 0 if the kernel chosen for this descriptor can apply accflow_conv_desc.in_norm */
 int accflow_conv_in_norm_supported(const accflow_conv_desc* desc);
+/* != 0 if the GRU epilogues can run on the pre-split state (accflow_conv_desc.e0_fmt / p32): the tap-specialised 5-tap
+ * direct route is on (environment switches ACCFLOW_DIRECT_KT, ACCFLOW_DIRECT_W4 not 0, ACCFLOW_S16M 0 or unset; read
+ * once per process).  Descriptors with e0_fmt or p32 set are refused (return 1) where this is 0. */
+int accflow_conv_gru16_supported(void);
 
 /* CorrBlock.corr + the 3 avg_pool2d levels (raft/corr.py:8-22, 47-55; gma/corr.py identical).
  * fmap1/fmap2: (B, C, H8, W8).  lvl[l]: (B*H8*W8, Hl, Wl) with Hl = H8 >> l (floor), fp32.

@@ -623,18 +623,21 @@ def test_update_block_vs_golden(ops, golden):
 
 @pytest.mark.parametrize("name", ["raft", "gma"])
 def test_estimator_c1_vs_golden_and_oracle(ops, golden, name):
-    """C1: 128x256, iters 1/4/12 (+flow_init); gate: mean EPE <= 1e-3 px vs the reference's outputs."""
+    """C1: 128x256, iters 1/4/12 (+flow_init); gate: mean EPE <= 1e-3 px vs the reference's outputs; max EPE about 4x the
+    largest measured on the MI355X (in the messages)."""
     g = golden(name + "_c1")
     m, sd = _models(name)
     i1, i2 = _pair(int(g["seed"]), int(g["H"]), int(g["W"]))
+    gate, measured = {"raft": (2e-4, 4.35e-5), "gma": (2e-3, 4.39e-4)}[name]
     for it in (1, 4, 12):
         out = m(dev(i1), dev(i2), iters=it).cpu()
         ref = T(g["flow_it%d" % it])
         me, mx = O.epe(out if it == 12 else out[:, :, ::2, ::2], ref)
-        assert me <= 1e-3 and mx <= 1e-2, (name, it, me, mx)
+        assert me <= 1e-3 and mx <= gate, (name, it, me, mx, "measured max %.2e" % measured)
     out = m(dev(i1), dev(i2), iters=4, flow_init=dev(T(g["flow_init"]))).cpu()
     me, mx = O.epe(out[:, :, ::2, ::2], T(g["flow_it4_init"]))
-    assert me <= 1e-3 and mx <= 1e-2, (name, "flow_init", me, mx)
+    gate, measured = {"raft": (1e-4, 2.01e-5), "gma": (1e-3, 1.49e-4)}[name]
+    assert me <= 1e-3 and mx <= gate, (name, "flow_init", me, mx, "measured max %.2e" % measured)
     # batch of 2 different pairs == two single calls (batching must not change results)
     j1, j2 = _pair(1001, int(g["H"]), int(g["W"]))
     both = m(dev(torch.cat([i1, j1])), dev(torch.cat([i2, j2])), iters=4).cpu()
@@ -655,7 +658,7 @@ def test_accflow_c1_vs_golden(ops, golden):
     assert len(outs) == int(g["n_frames"]) - 2
     for k, o in enumerate(outs):
         me, mx = O.epe(o.cpu(), T(g["out%d" % k]))
-        assert me <= 1e-3 and mx <= 2e-2, ("accflow out", k, me, mx)
+        assert me <= 1e-3 and mx <= 5e-4, ("accflow out", k, me, mx, "measured max 1.12e-4")
     # the step API of the reference (AccFlow.iter) gives the same first output
     small, up = model.iter(frames[2], frames[1], frames[0], None)
     check(small, T(g["s2_out_small"]), 2e-4, rtol=1e-3, what="iter out_small")
@@ -710,7 +713,7 @@ def test_raft_c2_480x1024_vs_reference(ops, golden):
     i1, i2 = _pair(int(g["seed"]), int(g["H"]), int(g["W"]))
     out = m(dev(i1), dev(i2), iters=12)
     me, mx = O.epe(out[:, :, ::8, ::8].cpu(), T(g["flow_it12_s8"]))
-    assert me <= 1e-3 and mx <= 2e-2, (me, mx)
+    assert me <= 1e-3 and mx <= 5e-4, (me, mx, "measured max 1.12e-4")
     assert bool(torch.isfinite(out).all())
 
 
@@ -728,7 +731,7 @@ def test_accflow_c3_7x480x1024_vs_reference(ops, golden):
     assert len(outs) == 5
     for k, o in enumerate(outs):
         me, mx = O.epe(o[:, :, ::8, ::8].cpu(), T(g["out%d" % k]))
-        assert me <= 1e-3 and mx <= 2e-2, (k, me, mx)
+        assert me <= 1e-3 and mx <= 2e-3, (k, me, mx, "measured max 2.94e-4")
     # a batch of two sequences == each alone (sequence sharding relies on it)
     frames2 = [dev(normalize(f)) for f in make_sequence(1000, 7, 480, 1024, batch=2)]
     outs2 = model(images=frames2)
@@ -818,7 +821,7 @@ def test_accflow_gma_c5_7x720x1280_vs_reference(ops, golden):
     for k, o in enumerate(outs):
         me, mx = O.epe(o[:, :, ::8, ::8].cpu(), T(g["out%d" % k]))
         print("C5 out%d: EPE mean %.2e max %.2e" % (k, me, mx))
-        assert me <= 1e-3 and mx <= 2e-2, (k, me, mx)
+        assert me <= 1e-3 and mx <= 5e-3, (k, me, mx, "measured max 1.00e-3")
 
 
 def test_c5_size_properties(ops):
@@ -1224,7 +1227,7 @@ def test_warm_start_vs_oracle(ops):
     for k, (o, r) in enumerate(zip(outs, refs)):
         me, mx = O.epe(o.cpu(), r)
         print("warm start out%d: EPE mean %.2e max %.2e" % (k, me, mx))
-        assert me <= 1e-3 and mx <= 2e-2, (k, me, mx)
+        assert me <= 1e-3 and mx <= 5e-4, (k, me, mx, "measured max 8.13e-5")
     ofe = model.ofe
     fi = torch.randn(2, 2, 16, 32, generator=g) * 0.5
     both = ofe.estimate_pairs([dev(f) for f in frames], [(2, 1), (3, 0)], iters=3, flow_init=dev(fi))

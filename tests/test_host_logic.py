@@ -332,3 +332,46 @@ def test_pair_group_cuts():
         assert c == [0, 5, 11] and ids[c[1]] != ids[c[1] - 1]
     ids2 = [(0, 0)] * 3 + [(1, 0)] * 3                                               # a cut inside a run moves to its end
     assert RAFTGMA._group_cuts(6, 2, ctx_ids=ids2) == [0, 3, 6] and RAFTGMA._group_cuts(6, 2, ctx_ids=[(0, 0)] * 4 + [(1, 0)] * 2) == [0, 4, 6]
+
+
+@pytest.mark.parametrize("name", ["raft", "gma"])
+def test_gru_state_gate_rejects_lost_bits(name):
+    """tests/test_gru_state.py's gate of one GRU iteration, on the CPU: a float64 state rounded like the kernels' pre-split
+    state (fp16 hi + lo of h * 2^4) after each half-step passes it; the same state with one lo bit dropped, or with hi only,
+    fails it - so the gate measures the state's 22 bits rather than only bounding them loosely."""
+    from test_gru_state import check_gate_discrimination, gru_inputs, gru_weights64, saturated_state_dict, state_rounding
+    _, sd = saturated_state_dict(name)
+    x_dim = 384 if name == "gma" else 256
+    rnd = state_rounding(11)          # (inputs representable by the pre-split format, as the kernels read them)
+    for shape in ((1, 16, 32), (2, 5, 33)):
+        hs, inp, rest = gru_inputs(*shape, x_dim, seed=300 + shape[2])
+        check_gate_discrimination(rnd(hs.double()), torch.cat([rnd(inp.double()), rnd(rest.double())], 1), gru_weights64(sd, "cpu"))
+
+
+@pytest.mark.parametrize("env,want", [({}, 1), ({"ACCFLOW_DIRECT_KT": "0"}, 0), ({"ACCFLOW_DIRECT_KT": "00"}, 0),
+                                      ({"ACCFLOW_DIRECT_KT": ""}, 0), ({"ACCFLOW_DIRECT_KT": "1"}, 1), ({"ACCFLOW_DIRECT_W4": "0"}, 0),
+                                      ({"ACCFLOW_S16M": "1"}, 0), ({"ACCFLOW_S16M": "0"}, 1), ({"ACCFLOW_S16M": ""}, 1)])
+def test_h16_state_decision_python_equals_library(env, want):
+    """Whether the GRU state lives pre-split only: the library decides (accflow_conv_gru16_supported, its switches read once
+    per process) and refuses a packed-operand descriptor where it says no, so update.h16_state_supported() must give the
+    same answer for every setting of the three switches - also after the environment changes inside the process - and add
+    only the Python-side condition (ACCFLOW_S16_VIA_MULTI=1: no)."""
+    import json
+    import subprocess
+    import sys
+    code = ("import json, os\n"
+            "from accflow_amd import _lib\n"
+            "from accflow_amd.networks.raft.update import h16_state_supported\n"
+            "a = [_lib.load().accflow_conv_gru16_supported(), h16_state_supported()]\n"
+            "for k in ('ACCFLOW_DIRECT_KT', 'ACCFLOW_DIRECT_W4', 'ACCFLOW_S16M'):\n"
+            "    os.environ[k] = '0' if os.environ.get(k, '1') != '0' else '1'\n"
+            "print(json.dumps(a + [_lib.load().accflow_conv_gru16_supported(), h16_state_supported()]))\n")
+    base = {k: v for k, v in os.environ.items() if k not in ("ACCFLOW_DIRECT_KT", "ACCFLOW_DIRECT_W4", "ACCFLOW_S16M",
+                                                             "ACCFLOW_S16_VIA_MULTI")}
+    for multi in ("0", "1"):
+        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, cwd=ROOT,
+                           env=dict(base, ACCFLOW_S16_VIA_MULTI=multi, **env))
+        assert r.returncode == 0, r.stderr[-2000:]
+        c0, py0, c1, py1 = json.loads(r.stdout.strip().splitlines()[-1])
+        assert c0 == c1 == want, (env, c0, c1)
+        assert py0 == py1 == (bool(want) and multi == "0"), (env, multi, py0, py1)
