@@ -12,6 +12,12 @@ region.  `--shard pairs` is the strong-scaling mode: one sequence per step sprea
 `--shard pairs-stream` the same over a stream of sequences with a rotating root (AccFlow.forward_pair_sharded_stream:
 sequence k's chain on rank k mod N underneath that rank's pairs of the following sequences).
 
+A plain run does only what the headline needs: set-up, the warm-up steps, the timed steps, --dump-outputs if given,
+and the JSON line.  `--full` adds everything else the benchmark measures or checks after the timed region: the
+single-stream roofline pass, one sequence at a time, two sequences per step, the pair-sharded code path on one rank,
+the bf16x6 run, EPE against the reference's outputs, the CPU baseline and the other configurations (C2, C5, the
+training step).  Neither changes the timed steps or their outputs.
+
 Prints ONE JSON line on rank 0 (see README / DESIGN.md for the fields).
 """
 import argparse
@@ -57,6 +63,10 @@ def parse():
                          "(AccFlow.forward_pair_sharded_stream: sequence k's chain on rank k %% world, underneath the next pairs)")
     ap.add_argument("--spawn", action="store_true",
                     help="start the --gpus ranks from this process even for N = 1 (default: only when N > 1 and no WORLD_SIZE)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run every side measurement and check (roofline pass, one sequence at a "
+                         "time, two sequences per step, pair-sharded path on one rank, bf16x6, parity vs the reference, CPU "
+                         "baseline, other configurations); the --no-* switches below leave out parts of it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--no-strict", action="store_true", help="skip the secondary bf16x6 measurement")
@@ -66,7 +76,8 @@ def parse():
     ap.add_argument("--no-extra", action="store_true", help="skip the C2 (single pair), C5 (GMA 720x1280) and training-step side measurements")
     ap.add_argument("--busy-json", default=os.path.join(ROOT, "profiles", "conv_mfma_busy.json"),
                     help="matrix-pipe counters of the conv kernels from a rocprofv3 --pmc pass (optional)")
-    ap.add_argument("--dump-kernels", default=None, help="write the per-conv-shape timing table to this file")
+    ap.add_argument("--dump-kernels", default=None, help="write the per-conv-shape timing table of the roofline pass to this "
+                                                          "file (needs --full)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="write rank 0's outputs of the last timed step (the accumulated flows F(k->0)) as DIR/flow_<k>_to_0.npy "
                          "in float32; above %d MB in all, a fixed seeded sample of each array" % (DUMP_CAP_BYTES // 10**6))
@@ -75,6 +86,8 @@ def parse():
     a = ap.parse_args()
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.dump_kernels and not a.full:
+        ap.error("--dump-kernels needs --full (the table comes from the roofline pass)")
     return a
 
 
@@ -354,9 +367,9 @@ def main():
     outs_host = [o.detach().float().cpu() for o in outs] if (a.dump_outputs and rank == 0 and outs is not None) else None
     # Per-kernel HIP-event timing for the roofline objects: PROF_STEPS extra steps of the same workload right
     # after the timed region, with the pair groups on ONE stream - in the timed region two streams overlap
-    # kernels, which makes a single kernel's event-to-event time meaningless.
-    timer = profiler.KernelTimer(["corr_lookup", "conv2d", "lookup_convc1"]) if rank == 0 else None
-    if rank == 0:
+    # kernels, which makes a single kernel's event-to-event time meaningless.  (--full only, as is every side figure below)
+    timer = profiler.KernelTimer(["corr_lookup", "conv2d", "lookup_convc1"]) if (rank == 0 and a.full) else None
+    if timer is not None:
         import accflow_amd.networks.raft.raft as _raft
         saved = _raft.N_STREAMS
         _raft.N_STREAMS = 1
@@ -380,7 +393,7 @@ def main():
 
     # Secondary figure: latency-style schedule, one sequence at a time (model(images) in a loop)
     unpiped = None
-    if pipe is not None:
+    if pipe is not None and a.full:
         step_local()
         fence()
         ts = time.perf_counter()
@@ -394,7 +407,7 @@ def main():
     # Secondary figure (rank 0 only, no collectives): TWO sequences per step (22 pairs per estimator launch) - what batching
     # independent sequences, as test_cvo.py's loader does (batch 10), buys on this workload
     batched = None
-    if rank == 0 and pipe is not None and S == 1 and not a.no_extra:
+    if rank == 0 and a.full and pipe is not None and S == 1 and not a.no_extra:
         two = [torch.cat([f, f2]) for f, f2 in zip(frames, [normalize(f).to(dev) for f in
                                                           make_sequence(5000, a.frames, a.height, a.width)])]
         pb = SequencePipeline(model)
@@ -412,7 +425,7 @@ def main():
         del two, pb
     # Secondary figure (N = 1, sequences mode): the strong-scaling code path - AccFlow.forward_pair_sharded - on ONE rank
     pair_one = None
-    if rank == 0 and world == 1 and not pairs_mode and not a.no_extra:
+    if rank == 0 and a.full and world == 1 and not pairs_mode and not a.no_extra:
         model.forward_pair_sharded(frames)
         torch.cuda.synchronize()
         ts = time.perf_counter()
@@ -438,7 +451,7 @@ def main():
     # the headline so that the cost of NOT using the fp16 operand split is on the same JSON line.
     strict = None
     from accflow_amd import ops as _ops
-    if _ops.conv_mode_name() == "f16x3" and not a.no_strict:
+    if a.full and _ops.conv_mode_name() == "f16x3" and not a.no_strict:
         _ops.set_conv_mode("bf16x6")
         step()
         fence()
@@ -461,7 +474,7 @@ def main():
         pair_evals = nseq * pairs_per_seq
         value = pair_evals / elapsed
         seq_s = nseq / elapsed
-        ks = timer.summary()
+        ks = timer.summary() if timer is not None else {}
         lk, cv, lf = ks.get("corr_lookup"), ks.get("conv2d"), ks.get("lookup_convc1")
         traffic = traffic_fused = None
         if os.path.exists(a.traffic_json):
@@ -471,13 +484,18 @@ def main():
                 traffic_fused = tj.get("fused", {}).get("hbm_bytes_per_launch")
             except Exception:
                 traffic = None
+        mode = _ops.conv_mode_name()
+        dtype = ("f32" if mode == "f32" else
+                 "f32 (direct-kernel operands split into 2 fp16 terms - activations kept pre-split in HBM as fp16 hi+lo, "
+                 "4 B per element; other kernels 3 bf16 terms; f32 accumulate)"
+                 if mode == "f16x3" else "f32 (operands split into bf16 terms, %s; f32 accumulate)" % mode)
         res = {
             "metric": "frame-pairs/s (estimator pair-evals/s), AccFlow(%s) %d-frame %dx%d backward accumulation"
                       % (a.ofe.upper(), a.frames, a.height, a.width),
             "value": round(value, 3), "unit": "frame-pairs/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": round(1e3 * elapsed / a.steps, 3), "higher_is_better": True,
             "scaling": "strong" if pairs_mode else "weak", "rccl_ranks": rccl_ranks,
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "vs_baseline": None, "dtype": dtype, "data": "synthetic",
             "config": {"workload": ("AccFlow(%s) %d-frame %dx%d, %d GRU iters, ONE sequence per step spread over all ranks "
                                     "(BASELINE.json configs[4] / the north-star's pair sharding when n_gpus=8)"
                                     % (a.ofe.upper(), a.frames, a.height, a.width, a.iters)) if pairs_mode else
@@ -508,17 +526,11 @@ def main():
                                              "value": round(world * S * pairs_per_seq / unpiped, 3),
                                              "note": "rank 0's clock, model(images) in a loop without the pipeline"}
         if cv:
-            from accflow_amd import ops as _ops
-            mode = _ops.conv_mode_name()
             tf = cv["work"] / (cv["total_ms"] * 1e-3) / 1e12
             tf_exec = cv["work_exec"] / (cv["total_ms"] * 1e-3) / 1e12
             # algorithmic fp32 conv flop; in the split-bf16 modes every product costs 3 / 6 bf16 MFMA flops, so
             # the ceiling for ALGORITHMIC flop/s is the dense bf16 MFMA peak divided by that factor
             peak = FP32_MFMA_PEAK_TF if mode == "f32" else BF16_MFMA_PEAK_TF / MFMAS_PER_PRODUCT[mode]
-            res["dtype"] = ("f32" if mode == "f32" else
-                            "f32 (direct-kernel operands split into 2 fp16 terms - activations kept pre-split in HBM as fp16 hi+lo, "
-                            "4 B per element; other kernels 3 bf16 terms; f32 accumulate)"
-                            if mode == "f16x3" else "f32 (operands split into bf16 terms, %s; f32 accumulate)" % mode)
             res["roofline"] = {"kernel": "implicit-GEMM conv kernels (%s, all instantiations)"
                                          % ("conv2d_f32_kernel" if mode == "f32" else
                                             "conv2d_direct_bf16s_kernel + conv2d_bf16s_kernel"), "conv_mode": mode,
@@ -620,13 +632,13 @@ def main():
                         d["work"] / (d["total_ms"] * 1e-3) / 1e12))
         if outs_host is not None:
             res["dumped_outputs"] = dump_outputs(outs_host, a.dump_outputs)
-        if not a.no_parity:
+        if a.full and not a.no_parity:
             res["parity"] = parity_vs_golden(outs, a)
         if strict is not None:
             res["strict_fp32_equivalent"] = strict
-        if not a.no_cpu_baseline and world == 1 and not pairs_mode:  # reported at N = 1 only (the other ranks would idle at the barrier)
+        if a.full and not a.no_cpu_baseline and world == 1 and not pairs_mode:  # reported at N = 1 only (the other ranks would idle at the barrier)
             res["cpu_baseline"] = cpu_baseline(a.iters, a.height, a.width, a.frames)
-        if not a.no_extra and world == 1 and not pairs_mode and (a.ofe, a.height, a.width) == ("raft", 480, 1024):
+        if a.full and not a.no_extra and world == 1 and not pairs_mode and (a.ofe, a.height, a.width) == ("raft", 480, 1024):
             del outs
             torch.cuda.empty_cache()
             try:

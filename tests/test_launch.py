@@ -102,14 +102,23 @@ def test_bench_rejects_gpus_world_mismatch():
     assert r.returncode != 0 and "--gpus 4 but WORLD_SIZE 2" in r.stderr
 
 
+def test_bench_dump_kernels_needs_full():
+    """The per-shape table comes from the roofline pass, which only a --full run makes: asking for it without --full is
+    an argument error, raised before any GPU call."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dump-kernels", os.devnull],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--dump-kernels needs --full" in r.stderr
+
+
 @pytest.mark.gpu
 @pytest.mark.timeout(900)
 def test_bench_pairs_mode_through_launcher():
     """bench.py --gpus 1 --spawn --shard pairs: the launcher path and the strong-scaling mode (forward_pair_sharded over
-    an RCCL group) end to end on the one GPU a box has; parity of its outputs vs the reference is in the JSON."""
+    an RCCL group) end to end on the one GPU a box has; parity of its outputs vs the reference is in the --full JSON."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--spawn", "--shard", "pairs",
-                        "--steps", "1", "--warmup", "1", "--no-strict"], capture_output=True, text=True, timeout=800, env=env)
+                        "--steps", "1", "--warmup", "1", "--full", "--no-strict"], capture_output=True, text=True, timeout=800,
+                       env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert d["n_gpus"] == 1 and d["rccl_ranks"] == 1 and d["scaling"] == "strong"

@@ -17,7 +17,7 @@ if [ "${1:-build}" = build ]; then
 else
   for m in 7 6 5 4; do
     lib=accflow_amd/lib/libaccflow_hip.so; [ $m != 7 ] && lib=tools/bin/lib_pm$m/libaccflow_hip.so
-    ACCFLOW_HIP_LIB=$lib timeout 900 python bench.py --no-strict --no-extra --no-cpu-baseline --steps 8 2> /dev/null | python -c "
+    ACCFLOW_HIP_LIB=$lib timeout 900 python bench.py --full --no-strict --no-extra --no-cpu-baseline --steps 8 2> /dev/null | python -c "
 import json, sys
 d = json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{')][-1])
 p = d['parity']

@@ -17,14 +17,14 @@ if [ "${1:-build}" = build ]; then
 else
   for m in 7 6 5; do
     lib=accflow_amd/lib/libaccflow_hip.so; [ $m != 7 ] && lib=tools/bin/lib_upm$m/libaccflow_hip.so
-    ACCFLOW_HIP_LIB=$lib timeout 900 python bench.py --no-strict --no-extra --no-cpu-baseline --steps 8 2> /dev/null | python -c "
+    ACCFLOW_HIP_LIB=$lib timeout 900 python bench.py --full --no-strict --no-extra --no-cpu-baseline --steps 8 2> /dev/null | python -c "
 import json, sys
 d = json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{')][-1])
 p = d['parity']
 print('C3 update-block PAIRMASK=$m (bit0 w_lo*x_hi, bit1 w_hi*x_lo, bit2 w_hi*x_hi): EPE vs reference mean %.2e max %.2e px | %.3f ms/step | one-at-a-time %.3f ms' % (p['epe_mean_px'], p['epe_max_px'], d['ms_per_step'], d['one_sequence_at_a_time']['ms_per_step']))
 "
     if [ "${2:-}" = c5 ]; then
-      ACCFLOW_HIP_LIB=$lib timeout 900 python bench.py --ofe gma --height 720 --width 1280 --no-strict --no-extra --no-cpu-baseline --steps 3 --warmup 1 2> /dev/null | python -c "
+      ACCFLOW_HIP_LIB=$lib timeout 900 python bench.py --full --ofe gma --height 720 --width 1280 --no-strict --no-extra --no-cpu-baseline --steps 3 --warmup 1 2> /dev/null | python -c "
 import json, sys
 d = json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{')][-1])
 p = d['parity']

@@ -6,10 +6,10 @@ O=gpurun_out/r03_run1
 mkdir -p $O
 timeout 900 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; echo "pytest rc $?" >> $O/pytest.log
 tail -5 $O/pytest.log
-timeout 600 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc $?"
-timeout 300 python bench.py --gpus 1 --spawn --shard pairs --steps 5 --warmup 2 --no-strict > $O/bench_pairs.json 2> $O/bench_pairs.err; echo "pairs rc $?"
+timeout 600 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc $?"
+timeout 300 python bench.py --gpus 1 --spawn --shard pairs --steps 5 --warmup 2 --full --no-strict > $O/bench_pairs.json 2> $O/bench_pairs.err; echo "pairs rc $?"
 for m in 6 5 4; do
-  ACCFLOW_HIP_LIB=$GRAFT_REPO_ROOT/tools/bin/lib_mask$m/libaccflow_hip.so timeout 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-strict --no-extra > $O/bench_mask$m.json 2> $O/bench_mask$m.err; echo "mask $m rc $?"
+  ACCFLOW_HIP_LIB=$PWD/tools/bin/lib_mask$m/libaccflow_hip.so timeout 300 python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-strict --no-extra > $O/bench_mask$m.json 2> $O/bench_mask$m.err; echo "mask $m rc $?"
 done
 python - <<'PY'
 import json,glob

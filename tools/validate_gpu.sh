@@ -4,7 +4,7 @@ cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/validate
 mkdir -p $O
 timeout 1800 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1; echo "pytest rc $?"; tail -6 $O/pytest.log
-timeout 600 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc $?"
+timeout 600 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc $?"
 python - <<'PY'
 import json
 d=json.loads([l for l in open("gpurun_out/validate/bench.json").read().strip().splitlines() if l.startswith("{")][-1])
