@@ -113,6 +113,10 @@ SIGNATURES = {
     "accflow_corr_disp_pool_f32": [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f],
     "accflow_corr_lookup_disp_f32": [c_f, c_f, c_f, c_f, c_f, c_f, c_ll, c_i, c_i, c_i, c_f],
     "accflow_corr_lookup_disp_s16": [c_f, c_f, c_f, c_f, c_f, c_f, c_ll, c_f, c_i, c_i, c_i, c_f],
+    "accflow_corr_alt_pyramid_elems": [c_i, c_i, c_i],
+    "accflow_corr_alt_pyramid_f32": [c_f, c_f, c_i, c_i, c_i, c_i, c_f],
+    "accflow_corr_lookup_alt_f32": [c_f, c_i, c_f, c_f, c_f, c_ll, c_i, c_i, c_i, c_i, c_f],
+    "accflow_corr_lookup_alt_s16": [c_f, c_i, c_f, c_f, c_f, c_ll, c_f, c_i, c_i, c_i, c_i, c_f],
     "accflow_corr_lookup_convc1_kpad": [],
     "accflow_corr_lookup_convc1_s16": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_ll, c_f, c_ll, c_i, c_f, c_i, c_i, c_i, c_i, c_f],
     "accflow_flow_from_coords_s16": [c_f, c_f, c_ll, c_f, c_ll, c_f, c_ll, c_f, c_ll, c_i, c_f, c_i, c_i, c_i, c_i, c_f],
@@ -187,7 +191,7 @@ def load():
             fn = getattr(lib, name)  # AttributeError if a declared symbol is missing
             fn.argtypes = argtypes
             fn.restype = ctypes.c_longlong if name in ("accflow_conv_patch_elems", "accflow_conv_multi_pack_elems", "accflow_corr_pack_bytes", "accflow_corr_volume_ws_bytes",
-                                                    "accflow_gma_aggregate_ws_bytes", "accflow_gma_attention_ws_bytes", "accflow_gma_aggregate_s16_ws_bytes", "accflow_gma_attention_s16_ws_bytes", "accflow_corr_disp_level_elems",
+                                                    "accflow_gma_aggregate_ws_bytes", "accflow_gma_attention_ws_bytes", "accflow_gma_aggregate_s16_ws_bytes", "accflow_gma_attention_s16_ws_bytes", "accflow_corr_disp_level_elems", "accflow_corr_alt_pyramid_elems",
                                                     "accflow_s16_item_words") else ctypes.c_int
         if lib.accflow_abi_version() != ABI_VERSION:
             raise RuntimeError("accflow_amd: ABI version mismatch")

@@ -4,6 +4,8 @@ Same constructor / call contract as the reference's networks/raft/corr.py:7-55 (
 `CorrBlock(fmap1, fmap2, num_levels=4, radius=4)` builds `corr_pyramid` (list of (B*H*W, 1, Hl, Wl)
 fp32 tensors) and `corr_fn(coords)` returns (B, num_levels*(2r+1)^2, H, W).
 """
+import torch
+
 from ... import ops
 from .._packs import require_cuda
 
@@ -78,3 +80,53 @@ class CorrBlock:
         B, _, H, W = fmap1.shape
         lvl0 = ops.corr_volume(fmap1.float().contiguous(), fmap2.float().contiguous())[0]
         return lvl0.view(B, H, W, 1, H, W)
+
+
+class AlternateCorrBlock:
+    """alternate_corr (the reference's args.alternate_corr, raft.py:45-46): CorrBlock's lookup computed on the fly from the
+    feature maps (csrc/corr_alt.hip) - per frame a pooled target pyramid of (H8*W8*C*4/3) floats instead of a volume of
+    ~(H8*W8)^2*4/3 per pair.  Same call surface as CorrBlock; the results agree up to fp32 rounding."""
+
+    def __init__(self, fmap1, fmap2, num_levels=4, radius=4):
+        if num_levels != 4 or radius != 4:
+            raise NotImplementedError("HIP AlternateCorrBlock is built for the reference's fixed 4 levels / radius 4")
+        require_cuda(fmap1, fmap2)
+        if fmap1.shape != fmap2.shape:
+            raise RuntimeError("AlternateCorrBlock: fmap1 %s and fmap2 %s differ" % (tuple(fmap1.shape), tuple(fmap2.shape)))
+        B = fmap1.shape[0]
+        frames = torch.cat([fmap1.float(), fmap2.float()], dim=0).contiguous()
+        self._init(ops.corr_alt_pyramid(frames), range(B), range(B, 2 * B))
+
+    def _init(self, pyr, idx1, idx2):
+        self.num_levels, self.radius = 4, 4
+        self._pairs = ops.AltPairs(pyr, idx1, idx2)
+
+    @classmethod
+    def from_frames(cls, fmaps, idx1, idx2):
+        """Pairs (query frame idx1[b], target frame idx2[b]) of frame-major features (F, C, H8, W8): the counterpart of
+        CorrBlock.from_packs (AccFlow: one pyramid of 7 frames for 11 pairs).  fmaps may also be a built ops.AltPyramid."""
+        self = cls.__new__(cls)
+        if not isinstance(fmaps, ops.AltPyramid):
+            require_cuda(fmaps)
+            fmaps = ops.corr_alt_pyramid(fmaps.float().contiguous())
+        self._init(fmaps, idx1, idx2)
+        return self
+
+    @property
+    def corr_pyramid(self):
+        raise AttributeError("AlternateCorrBlock has no correlation pyramid: it computes the lookup from the feature maps "
+                             "(that is its point); use CorrBlock for the reference's corr_pyramid")
+
+    def supports_s16(self):
+        return True
+
+    def lookup_s16(self, coords, out16, cache=None):
+        """The lookup written pre-split, as CorrBlock.lookup_s16 (ops.corr_lookup_alt_s16); cache: see ops.conv2d."""
+        if cache is not None and cache[1] in cache[0]:
+            return ops.corr_lookup_alt_s16(self._pairs, coords, out16, cache=cache)
+        require_cuda(coords)
+        return ops.corr_lookup_alt_s16(self._pairs, coords.float().contiguous(), out16, cache=cache)
+
+    def __call__(self, coords, out=None):
+        require_cuda(coords)
+        return ops.corr_lookup_alt(self._pairs, coords.float().contiguous(), out=out)

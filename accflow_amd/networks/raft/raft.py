@@ -22,7 +22,7 @@ import torch.nn as nn
 from ... import ops
 from .._packs import require_cuda
 from . import corr as _corr
-from .corr import CorrBlock
+from .corr import AlternateCorrBlock, CorrBlock
 from .extractor import BasicEncoder
 from . import update as _update
 from .update import BasicUpdateBlock, UpdateWorkspace
@@ -35,6 +35,8 @@ N_STREAMS = max(1, int(os.environ.get("ACCFLOW_STREAMS", "2")))
 # kernel ALONE (accflow_corr_lookup_disp_s16, same pyramid, same coords) is launched in addition there to be timed
 PROFILE_STANDALONE_LOOKUP = False
 USE_CORR_PACKS = os.environ.get("ACCFLOW_CORR_PACKS", "1") == "1"   # per-frame correlation operand packs (0: per pair, A/B)
+# alternate_corr for every estimator (as if each one's args.alternate_corr were set): the lookup from the feature maps, no volume
+ALTERNATE_CORR = os.environ.get("ACCFLOW_ALTERNATE_CORR", "0") == "1"
 _STREAMS = {}
 
 
@@ -98,6 +100,10 @@ class RAFT(nn.Module):
     def _x_dim(self):
         return 256
 
+    def _alternate(self):
+        """alternate_corr (raft.py:45-46), read at forward time: AlternateCorrBlock instead of the correlation volume."""
+        return ALTERNATE_CORR or bool(getattr(self.args, "alternate_corr", False))
+
     def _prepack(self):
         """All weight packs the refinement loop uses, built on the current (main) stream before the fork."""
         self.update_block.prepack()
@@ -118,7 +124,7 @@ class RAFT(nn.Module):
         if ws.s16 and corr_fn.supports_s16():
             # (coords1 is updated in place by the flow head: the same tensors in every iteration -> cached launches)
             ub = self.update_block
-            if _update.FUSE_LOOKUP and ub.encoder.convc1.out_channels == 256:
+            if _update.FUSE_LOOKUP and ub.encoder.convc1.out_channels == 256 and isinstance(corr_fn, CorrBlock):
                 # relu(convc1(lookup)) in one kernel: the taps go through LDS into the matrix cores, not through HBM
                 if PROFILE_STANDALONE_LOOKUP and ops.profiler.ACTIVE is not None:
                     corr_fn.lookup_s16(coords1, ws.corr16)    # (bench.py's roofline pass only: the north-star kernel alone)
@@ -164,7 +170,8 @@ class RAFT(nn.Module):
         if iters < 1:  # the reference would raise NameError on `flow_up`; be explicit
             raise ValueError("iters must be >= 1")
         # packed = (ops.CorrPacks, idx1, idx2): per-frame operand packs of the correlation GEMM + the frame of each
-        # pair's queries / targets, instead of pair-major copies of the feature maps
+        # pair's queries / targets, instead of pair-major copies of the feature maps; (ops.AltPyramid, idx1, idx2): the same
+        # for alternate_corr
         indexed = isinstance(cnet_feat, tuple)     # (frame-major features, per-item indices)
         B = len(cnet_feat[1]) if indexed else cnet_feat.shape[0]
         dev = (cnet_feat[0] if indexed else cnet_feat).device
@@ -199,10 +206,13 @@ class RAFT(nn.Module):
                 else:
                     st.wait_stream(main)
             with torch.cuda.stream(st):
-                if packed is not None:
+                if packed is not None and isinstance(packed[0], ops.AltPyramid):
+                    corr_fn = AlternateCorrBlock.from_frames(packed[0], packed[1][b0:b1], packed[2][b0:b1])
+                elif packed is not None:
                     corr_fn = CorrBlock.from_packs(packed[0], packed[1][b0:b1], packed[2][b0:b1])
                 else:
-                    corr_fn = CorrBlock(fmap1[b0:b1], fmap2[b0:b1], radius=self.args.corr_radius)
+                    block = AlternateCorrBlock if self._alternate() else CorrBlock
+                    corr_fn = block(fmap1[b0:b1], fmap2[b0:b1], radius=self.args.corr_radius)
                 if early and ctx_ready is not None:
                     st.wait_event(ctx_ready)  # the context features and the update block's packs (split mode: no flow_init)
                 elif early:
@@ -309,10 +319,9 @@ class RAFT(nn.Module):
             ready = (ready, home[0], home[1])
         return self._estimate_encoded(frames, pairs, feats, ready, iters, flow_init)
 
-    @staticmethod
-    def _packs_usable(feats, pairs):
+    def _packs_usable(self, feats, pairs):
         fb = feats.get("fmap_base")
-        return (fb is not None and USE_CORR_PACKS and _corr.LAYOUT == "disp" and all(f in fb[1] for p in pairs for f in p)
+        return (fb is not None and USE_CORR_PACKS and not self._alternate() and _corr.LAYOUT == "disp" and all(f in fb[1] for p in pairs for f in p)
                 and ops.corr_packs_supported(fb[0].shape[1], fb[0].shape[2], fb[0].shape[3]))
 
     @torch.no_grad()
@@ -358,6 +367,16 @@ class RAFT(nn.Module):
                 raise RuntimeError("estimate_pairs: flow_init must be (len(pairs)*N, 2, H/8, W/8)")
         ctx_ids = [(i, n) for i, _ in pairs for n in range(N)]  # pairs out of the same frame share context features
         fb = feats.get("fmap_base")
+        if self._alternate() and fb is not None and all(f in fb[1] for p in pairs for f in p):
+            # alternate_corr: ONE target pyramid of the frame-major features serves every pair (no volume, no packs)
+            idx1 = [fb[1][i] * N + n for i, _ in pairs for n in range(N)]
+            idx2 = [fb[1][j] * N + n for _, j in pairs for n in range(N)]
+
+            def refine_alt():
+                pyr = ops.corr_alt_pyramid(fb[0])
+                return self._refine(None, None, cfeat, iters, flow_init, packed=(pyr, idx1, idx2), ctx_ids=ctx_ids)
+
+            return ops.with_range_guard(refine_alt, frames[0].device, name="%s.refine" % type(self).__name__)
         if self._packs_usable(feats, pairs):
             # the feature maps stay frame-major: each frame is split ONCE into the correlation GEMM's operand pack
             # (7 packs for the 11 pairs of a 7-frame sequence; no pair-major copies)

@@ -1221,6 +1221,114 @@ def corr_disp_pool(lvl0, H8, W8):
     return DispPyramid(lv, B, H8, W8)
 
 
+class AltPyramid:
+    """Target pyramid of the on-the-fly lookup (alternate_corr, csrc/corr_alt.hip): level l of F frames as (F, H8>>l, W8>>l, C)
+    channel-last blocks in one buffer - O(F*P) floats where the volume holds O(B*P^2).  `levels()` gives views (tests)."""
+    __slots__ = ("data", "F", "C", "H8", "W8")
+
+    def __init__(self, data, F, C, H8, W8):
+        self.data, self.F, self.C, self.H8, self.W8 = data, F, C, H8, W8
+
+    def levels(self):
+        out, off = [], 0
+        for (h, w) in corr_pyramid_shapes(self.H8, self.W8):
+            n = self.F * h * w * self.C
+            out.append(self.data[off:off + n].view(self.F, h, w, self.C))
+            off += n
+        return out
+
+
+def corr_alt_pyramid(fmaps):
+    """Frame-major features (F, C, H8, W8) -> AltPyramid (once per frame; any number of pairs then index it)."""
+    lib = _lib.load()
+    fmaps = _dense(fmaps, "fmaps")
+    F, C, H8, W8 = fmaps.shape
+    if C < 16 or C % 16 or H8 < 8 or W8 < 8:
+        raise RuntimeError("corr_alt_pyramid: needs C % 16 == 0 and H8, W8 >= 8 (got %s)" % (tuple(fmaps.shape),))
+    data = torch.empty(F * lib.accflow_corr_alt_pyramid_elems(C, H8, W8), dtype=torch.float32, device=fmaps.device)
+    _check(lib.accflow_corr_alt_pyramid_f32(_p(fmaps), _p(data), F, C, H8, W8, _stream()), "accflow_corr_alt_pyramid_f32")
+    return AltPyramid(data, F, C, H8, W8)
+
+
+class AltPairs:
+    """Items (query frame idx1[b], target frame idx2[b]) of an AltPyramid: the frame indices live on the device (the lookup
+    kernel reads them; 2B ints, checked here)."""
+    __slots__ = ("pyr", "B", "idx")
+
+    def __init__(self, pyr, idx1, idx2):
+        idx1, idx2 = [int(i) for i in idx1], [int(i) for i in idx2]
+        if not idx1 or len(idx2) != len(idx1) or min(idx1 + idx2) < 0 or max(idx1 + idx2) >= pyr.F:
+            raise RuntimeError("AltPairs: bad frame indices")
+        self.pyr, self.B = pyr, len(idx1)
+        dev = pyr.data.device
+        if torch.cuda.is_current_stream_capturing():
+            # (no host-to-device copy inside a graph capture - the training step captures its forward: fills are kernels
+            # whose values the graph keeps)
+            self.idx = torch.empty(2 * self.B, dtype=torch.int32, device=dev)
+            for k, v in enumerate(idx1 + idx2):
+                self.idx[k].fill_(v)
+        else:
+            self.idx = torch.tensor(idx1 + idx2, dtype=torch.int32, device=dev)
+
+
+def _alt_checked(pairs, coords, name):
+    if not isinstance(pairs, AltPairs):
+        raise RuntimeError("%s: expected ops.AltPairs" % name)
+    coords = _dense(coords, "coords")
+    p = pairs.pyr
+    if tuple(coords.shape) != (pairs.B, 2, p.H8, p.W8):
+        raise RuntimeError("%s: coords %s do not match the pairs (%d, 2, %d, %d)" % (name, tuple(coords.shape), pairs.B, p.H8, p.W8))
+    return coords
+
+
+def corr_lookup_alt(pairs, coords, out=None, cache=None):
+    """The CorrBlock lookup (B, 324, H8, W8) computed on the fly from an AltPyramid; cache: see ops.conv2d."""
+    r = _replay(cache, "accflow_corr_lookup_alt_f32")
+    if r is not None:
+        return r
+    lib = _lib.load()
+    coords = _alt_checked(pairs, coords, "corr_lookup_alt")
+    p = pairs.pyr
+    B, H8, W8 = pairs.B, p.H8, p.W8
+    if out is None:
+        out = torch.empty((B, 324, H8, W8), dtype=torch.float32, device=coords.device)
+    out_bs = _plane4(out, "out")
+    if tuple(out.shape) != (B, 324, H8, W8):
+        raise RuntimeError("corr_lookup_alt: out shape %s" % (tuple(out.shape),))
+    tm = profiler.ACTIVE
+    t0 = tm.begin() if tm is not None and tm.wants("corr_lookup") else None
+    args = (_p(p.data), p.F, _p(pairs.idx), _p(coords), _p(out), out_bs, B, p.C, H8, W8)
+    _check(lib.accflow_corr_lookup_alt_f32(*args, _stream()), "accflow_corr_lookup_alt_f32")
+    if t0 is not None:
+        tm.end("corr_lookup", t0, LOOKUP_BYTES_PER_PX * B * H8 * W8, "alt B%d %dx%d" % (B, H8, W8))
+    elif cache is not None and tm is None:
+        cache[0][cache[1]] = (lib.accflow_corr_lookup_alt_f32, args, out, (pairs, coords, out))
+    return out
+
+
+def corr_lookup_alt_s16(pairs, coords, out16, cache=None):
+    """corr_lookup_alt written pre-split in corr_lookup_s16's channel order (the input of convc1's lookup88 pack)."""
+    r = _replay(cache, "accflow_corr_lookup_alt_s16")
+    if r is not None:
+        return r
+    lib = _lib.load()
+    coords = _alt_checked(pairs, coords, "corr_lookup_alt_s16")
+    p = pairs.pyr
+    B, H8, W8 = pairs.B, p.H8, p.W8
+    if tuple(out16.shape) != (B, LOOKUP_S16_CHANNELS, H8, W8):
+        raise RuntimeError("corr_lookup_alt_s16: shape mismatch")
+    tm = profiler.ACTIVE
+    t0 = tm.begin() if tm is not None and tm.wants("corr_lookup") else None
+    args = (_p(p.data), p.F, _p(pairs.idx), _p(coords), ctypes.c_void_p(out16.ptr()), out16.bs, _p(_guard(coords.device)),
+            B, p.C, H8, W8)
+    _check(lib.accflow_corr_lookup_alt_s16(*args, _stream()), "accflow_corr_lookup_alt_s16")
+    if t0 is not None:
+        tm.end("corr_lookup", t0, LOOKUP_BYTES_PER_PX * B * H8 * W8, "alt s16 B%d %dx%d" % (B, H8, W8))
+    elif cache is not None and tm is None:
+        cache[0][cache[1]] = (lib.accflow_corr_lookup_alt_s16, args, out16, (pairs, coords, out16))
+    return out16
+
+
 def corr_lookup(pyramid, coords, out=None):
     if isinstance(pyramid, DispPyramid):
         return _corr_lookup_alt(pyramid, coords, out, "accflow_corr_lookup_disp_f32")

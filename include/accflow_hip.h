@@ -349,6 +349,22 @@ int accflow_corr_lookup_disp_s16(const float* lvl0, const float* lvl1, const flo
                                  const float* coords, void* out16, long long out16_bs, int* guard, int B, int H8,
                                  int W8, void* stream);
 
+/* alternate_corr (raft/raft.py:45-46): the same lookup computed on the fly from the feature maps, with no volume.
+ * accflow_corr_alt_pyramid_f32 turns frame-major features fmaps (F, C, H8, W8) into the target pyramid pyr: level l of all F
+ * frames is an (F, H8>>l, W8>>l, C) channel-last block (level 0 = the features, level l+1 = F.avg_pool2d(level l, 2, 2)), the
+ * four blocks one after the other; F x accflow_corr_alt_pyramid_elems(C, H8, W8) floats.  C % 16 == 0, H8, W8 >= 8.
+ * accflow_corr_lookup_alt_f32 then writes out[b] = the lookup of accflow_corr_lookup_f32 in the volume of queries = frame
+ * idx[b] and targets = frame idx[B + b] (idx: DEVICE array of 2B ints, each in [0, F); an item with an index outside
+ * writes nothing), level l being (f1 . pool_l(f2)) / sqrt(C) in fp32 FMA arithmetic; same coordinate handling (out-of-range,
+ * integer and non-finite coords).  accflow_corr_lookup_alt_s16 writes the pre-split form of accflow_corr_lookup_disp_s16
+ * (same channel order, same split, same guard report). */
+long long accflow_corr_alt_pyramid_elems(int C, int H8, int W8);
+int accflow_corr_alt_pyramid_f32(const float* fmaps, float* pyr, int F, int C, int H8, int W8, void* stream);
+int accflow_corr_lookup_alt_f32(const float* pyr, int F, const int* idx, const float* coords, float* out, long long out_bs,
+                                int B, int C, int H8, int W8, void* stream);
+int accflow_corr_lookup_alt_s16(const float* pyr, int F, const int* idx, const float* coords, void* out16, long long out16_bs,
+                                int* guard, int B, int C, int H8, int W8, void* stream);
+
 /* CorrBlock.__call__ FUSED with BasicMotionEncoder's first convolution (raft/corr.py:24-45 -> raft/update.py:89-90,
  * `cor = relu(convc1(corr))`; gma/update.py identical): the 4 x 81 blended taps never reach HBM - they are the reduction
  * axis of the 1x1 convolution and go from the lanes that computed them through LDS into the matrix cores; only
