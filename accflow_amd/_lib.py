@@ -125,6 +125,7 @@ SIGNATURES = {
     "accflow_compose_flow_f32": [c_f, c_ll, c_f, c_ll, c_f, c_ll, c_i, c_i, c_i, c_f],
     "accflow_get_occ_f32": [c_f, c_ll, c_f, c_ll, c_f, c_ll, c_f, c_ll, c_i, c_i, c_i, c_i, c_i, c_f],
     "accflow_downflow8_f32": [c_f, c_f, c_i, c_i, c_i, c_i, c_f],
+    "accflow_forward_interpolate_f32": [c_f, c_f, c_i, c_i, c_i, c_f],
     "accflow_instance_norm_f32": [c_f, c_f, c_f, c_i, c_i, c_i, ctypes.c_float, c_i, c_f],
     "accflow_split_tanh_relu_f32": [c_f, c_f, c_ll, c_f, c_ll, c_i, c_i, c_i, c_i, c_f],
     "accflow_split_tanh_relu_idx_f32": [c_f, c_i, ctypes.POINTER(c_i), c_f, c_ll, c_f, c_ll, c_i, c_i, c_i, c_i, c_f],

@@ -1,1 +1,1 @@
-from ...raft.utils.utils import backwarp, coords_grid  # noqa: F401
+from ...raft.utils.utils import backwarp, coords_grid, forward_interpolate  # noqa: F401

@@ -160,13 +160,15 @@ class RAFT(nn.Module):
                     cuts[g] += 1
         return cuts
 
-    def _refine(self, fmap1, fmap2, cnet_feat, iters, flow_init, packed=None, ctx_ids=None, ready=None):
+    def _refine(self, fmap1, fmap2, cnet_feat, iters, flow_init, packed=None, ctx_ids=None, ready=None, return_low=False):
         """Correlation pyramid + `iters` refinement steps + convex upsampling for a batch of pairs.
 
         Batches of >= 4 pairs are processed as N_STREAMS independent groups on separate HIP streams: the pairs do
         not interact, and with two kernel sequences in flight the tail of one group's kernel (1 320 workgroups on
         768 resident slots = 1.7 rounds at B = 11) is back-filled by the other group's next kernel instead of
-        idling the chip until the next launch."""
+        idling the chip until the next launch.
+
+        return_low: also return the final 1/8-resolution flow coords1 - coords0 of every item, (B, 2, h, w)."""
         if iters < 1:  # the reference would raise NameError on `flow_up`; be explicit
             raise ValueError("iters must be >= 1")
         # packed = (ops.CorrPacks, idx1, idx2): per-frame operand packs of the correlation GEMM + the frame of each
@@ -191,6 +193,7 @@ class RAFT(nn.Module):
         streams = [main] if n_groups == 1 else _side_streams(dev, n_groups)
         # every group upsamples into its slice of ONE output tensor (allocated on the main stream before the fork)
         out_all = torch.empty((B, 2, 8 * h, 8 * w), dtype=torch.float32, device=dev)
+        low_all = torch.empty((B, 2, h, w), dtype=torch.float32, device=dev) if return_low else None
         forked = None
         if ctx_ready is not None:    # (a group that never waits for `main` must not write out_all before main's earlier readers)
             forked = torch.cuda.Event()
@@ -234,9 +237,11 @@ class RAFT(nn.Module):
                     st.wait_event(forked)
                 ops.flow_from_coords(coords1, dst0=ws.flow)
                 ops.convex_upsample(ws.flow, masks[g], out=out_all[bounds[g][0]:bounds[g][1]])
+                if return_low:
+                    low_all[bounds[g][0]:bounds[g][1]].copy_(ws.flow)
             if st != main:
                 main.wait_stream(st)
-        return out_all
+        return (out_all, low_all) if return_low else out_all
 
     @torch.no_grad()
     def forward(self, image1, image2, iters=12, flow_init=None):
@@ -305,11 +310,13 @@ class RAFT(nn.Module):
         return feats
 
     @torch.no_grad()
-    def estimate_pairs(self, frames, pairs, iters=12, flow_init=None, features=None):
+    def estimate_pairs(self, frames, pairs, iters=12, flow_init=None, features=None, return_low=False):
         """frames: list of (N,3,H,W); pairs: list of (i, j) = flow from frame i to frame j.
         flow_init: optional (len(pairs)*N, 2, H/8, W/8) start flows, pair-major (raft.py:123-124 per pair);
         features: encoder outputs from encode_frames to reuse across calls (warm-start chaining).
-        Returns (len(pairs)*N, 2, H, W), pair-major like torch.cat of per-pair calls."""
+        Returns (len(pairs)*N, 2, H, W), pair-major like torch.cat of per-pair calls; with return_low a tuple of that and
+        the 1/8-resolution flow coords1 - coords0 it was upsampled from, (len(pairs)*N, 2, H/8, W/8) - what
+        ops.forward_interpolate turns into the next pair's flow_init (estimate_video)."""
         require_cuda(*frames)
         N = frames[0].shape[0]
         feats = self.encode_pairs(frames, pairs, features)
@@ -317,7 +324,36 @@ class RAFT(nn.Module):
         home = feats.pop("refine_at_home", None)     # (ctx event, flip) of parallel.SequencePipeline's split mode
         if ready is not None and home is not None and flow_init is None:
             ready = (ready, home[0], home[1])
-        return self._estimate_encoded(frames, pairs, feats, ready, iters, flow_init)
+        return self._estimate_encoded(frames, pairs, feats, ready, iters, flow_init, return_low)
+
+    @torch.no_grad()
+    def estimate_video(self, frames, iters=12, warm_start=True, pairs=None, features=None):
+        """Flows over a frame stream with RAFT's warm start: frames = list of (N,3,H,W), pairs defaults to the adjacent
+        ones [(t, t+1)].  Every frame is encoded once.  warm_start=False: ONE batched estimate_pairs call.  warm_start=True:
+        the pairs run one after the other, and pair k > 0 starts from ops.forward_interpolate of pair k-1's 1/8-resolution
+        flow (the demo / Sintel loop of the reference, `flow_prev = forward_interpolate(flow_low[0])[None].cuda()`) - on the
+        device, with no host synchronisation beyond estimate_pairs' own.  iters: an int, or (first, rest) so that the
+        warm-started pairs run fewer iterations than the cold first one (warm_start=False has no warm-started pair: `first`).
+        Returns (flow_up, flow_low) = (len(pairs)*N, 2, H, W) and (len(pairs)*N, 2, H/8, W/8), pair-major.  (AccFlow's
+        warm_start is another thing: it composes flows backwards along the accumulation chain.)"""
+        require_cuda(*frames)
+        if pairs is None:
+            pairs = [(t, t + 1) for t in range(len(frames) - 1)]
+        pairs = list(pairs)
+        if not pairs:
+            raise ValueError("estimate_video: needs at least two frames (one pair)")
+        first, rest = (int(iters[0]), int(iters[1])) if isinstance(iters, (tuple, list)) else (iters, iters)
+        feats = self.encode_pairs(frames, pairs, features)
+        if not warm_start:
+            return self.estimate_pairs(frames, pairs, first, features=feats, return_low=True)
+        ups, lows = [], []
+        for k, pair in enumerate(pairs):
+            seed = ops.forward_interpolate(lows[-1]) if lows else None
+            up, low = self.estimate_pairs(frames, [pair], first if k == 0 else rest, flow_init=seed, features=feats,
+                                          return_low=True)
+            ups.append(up)
+            lows.append(low)
+        return torch.cat(ups, dim=0), torch.cat(lows, dim=0)
 
     def _packs_usable(self, feats, pairs):
         fb = feats.get("fmap_base")
@@ -350,7 +386,7 @@ class RAFT(nn.Module):
         self._prepack()      # (first call: the refinement loop's weight packs, on the stream the encoders ran on)
         return feats
 
-    def _estimate_encoded(self, frames, pairs, feats, ready, iters, flow_init):
+    def _estimate_encoded(self, frames, pairs, feats, ready, iters, flow_init, return_low=False):
         N = frames[0].shape[0]
         cb = feats.get("cnet_base")
         if cb is not None and all(i in cb[1] for i, _ in pairs):
@@ -374,7 +410,8 @@ class RAFT(nn.Module):
 
             def refine_alt():
                 pyr = ops.corr_alt_pyramid(fb[0])
-                return self._refine(None, None, cfeat, iters, flow_init, packed=(pyr, idx1, idx2), ctx_ids=ctx_ids)
+                return self._refine(None, None, cfeat, iters, flow_init, packed=(pyr, idx1, idx2), ctx_ids=ctx_ids,
+                                    return_low=return_low)
 
             return ops.with_range_guard(refine_alt, frames[0].device, name="%s.refine" % type(self).__name__)
         if self._packs_usable(feats, pairs):
@@ -393,12 +430,13 @@ class RAFT(nn.Module):
                 if cp is None or cp.mode != ops.current_mode():
                     cp, ev = ops.corr_pack(fb[0]), None
                     feats["corr_packs"] = cp
-                return self._refine(None, None, cfeat, iters, flow_init, packed=(cp, idx1, idx2), ctx_ids=ctx_ids, ready=ev)
+                return self._refine(None, None, cfeat, iters, flow_init, packed=(cp, idx1, idx2), ctx_ids=ctx_ids, ready=ev,
+                                    return_low=return_low)
 
             return ops.with_range_guard(refine_packed, frames[0].device, name="%s.refine" % type(self).__name__)
         fmap1 = torch.cat([feats["fmap"][i] for i, _ in pairs], dim=0)
         fmap2 = torch.cat([feats["fmap"][j] for _, j in pairs], dim=0)
-        return self._refine_guarded(fmap1, fmap2, cfeat, iters, flow_init, ctx_ids=ctx_ids)
+        return self._refine_guarded(fmap1, fmap2, cfeat, iters, flow_init, ctx_ids=ctx_ids, return_low=return_low)
 
 
 def default_args():

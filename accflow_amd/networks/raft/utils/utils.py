@@ -1,4 +1,4 @@
-"""Helpers the estimators import (reference: networks/raft/utils/utils.py:66-126), HIP-backed."""
+"""Helpers the estimators import (reference: networks/raft/utils/utils.py:31-126), HIP-backed."""
 from .... import ops
 from ..._packs import require_cuda
 
@@ -40,6 +40,16 @@ class InputPadder:
         ht, wd = x.shape[-2:]
         c = [self._pad[2], ht - self._pad[3], self._pad[0], wd - self._pad[1]]
         return x[..., c[0]:c[1], c[2]:c[3]]
+
+
+def forward_interpolate(flow):
+    """The warm start of a video loop (reference utils.py:31-63): the (2, h, w) 1/8-resolution flow of pair (t, t+1) pushed
+    forward along itself, holes filled from the nearest source; seeds pair (t+1, t+2) through `flow_init`.  Also takes a
+    (B, 2, h, w) batch.  Returns float32 ON THE INPUT'S DEVICE - the reference returns a CPU tensor after a round trip
+    through scipy, and a caller's `forward_interpolate(flow_low[0])[None].cuda()` works either way.  An item without a
+    source inside the frame gives zeros (the reference raises inside scipy).  One HIP kernel: ops.forward_interpolate."""
+    require_cuda(flow)
+    return ops.forward_interpolate(flow)
 
 
 def bilinear_sampler(img, coords, mode="bilinear", mask=False):

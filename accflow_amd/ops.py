@@ -1579,6 +1579,37 @@ def downflow8(flow):
     return out
 
 
+def forward_interpolate(flow, out=None):
+    """RAFT's warm start (raft/utils/utils.py:31-63) on the device: every cell of a 1/8-resolution flow is pushed along itself,
+    and every grid cell takes the flow of the nearest source that stayed strictly inside the frame.  flow: (B, 2, h, w) or
+    (2, h, w), any float dtype, channel 0 = x; returns float32 of the same shape on the same device (`out`: a contiguous
+    float32 tensor of that shape to write into, which must not overlap `flow`).  Positions and distances in double like the reference's,
+    exact ties to the lowest row-major source index; an item without a valid source (non-finite flows count as invalid) is all
+    zeros, where the reference raises inside scipy."""
+    lib = _lib.load()
+    if not (isinstance(flow, torch.Tensor) and flow.is_cuda and flow.is_floating_point() and flow.dim() in (3, 4)
+            and flow.shape[-3] == 2):
+        raise RuntimeError("forward_interpolate: expected a (B, 2, h, w) or (2, h, w) floating-point CUDA tensor, got %s" % (
+            (tuple(flow.shape), flow.dtype, flow.device) if isinstance(flow, torch.Tensor) else type(flow),))
+    shape = tuple(flow.shape)
+    src = _dense(flow.float().contiguous(), "flow")
+    h, w = shape[-2:]
+    B = shape[0] if len(shape) == 4 else 1
+    if B * h * w == 0:
+        raise RuntimeError("forward_interpolate: empty flow %s" % (shape,))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=flow.device)
+    else:
+        # (every workgroup reads ALL of the item's flows: `out` may not share a byte with the tensor the kernel reads)
+        nbytes = 4 * src.numel()
+        if (tuple(_dense(out, "out").shape) != shape or out.device != flow.device
+                or (out.data_ptr() < src.data_ptr() + nbytes and src.data_ptr() < out.data_ptr() + nbytes)):
+            raise RuntimeError("forward_interpolate: out must be a float32 tensor of shape %s on %s that does not overlap flow" % (
+                shape, flow.device))
+    _check(lib.accflow_forward_interpolate_f32(_p(src), _p(out), B, h, w, _stream()), "accflow_forward_interpolate_f32")
+    return out
+
+
 def instance_stats_finalize(stats, eps=1e-5, c0=0, C=None):
     """(B, C, 2) {mean, 1/sqrt(var + eps)} of every plane from a ConvStats (deterministic fixed-order merge); c0 / C: of the
     channels [c0, c0 + C) only (the two convolutions of a PackedMulti.from_strided_with_projection launch share one

@@ -412,6 +412,8 @@ int accflow_get_occ_s16(const float* flow, long long flow_bs, const float* i1, l
 
 /* downflow8 (AccFlow_.py:138-142): bilinear align_corners resize to (H/8, W/8), then / 8. */
 int accflow_downflow8_f32(const float* flow, float* out, int B, int C, int H, int W, void* stream);
+/* forward_interpolate (raft/utils/utils.py:31-63): nearest kept source of the flow pushed along itself; flow, out (B,2,H8,W8), not overlapping. */
+int accflow_forward_interpolate_f32(const float* flow, float* out, int B, int H8, int W8, void* stream);
 
 /* InstanceNorm2d (no affine, eps, biased var; extractor.py:36-39) over each (b,c) plane of `x`,
  * fused with what follows it in ResidualBlock.forward (extractor.py:56-63):

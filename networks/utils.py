@@ -1,1 +1,1 @@
-from accflow_amd.networks.utils import backwarp, coords_grid  # noqa: F401
+from accflow_amd.networks.utils import backwarp, coords_grid, forward_interpolate  # noqa: F401
