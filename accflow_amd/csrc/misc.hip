@@ -3,58 +3,57 @@
 
 namespace {
 
-__device__ __forceinline__ float wave_sum(float v) {
+__device__ __forceinline__ double block_sum(double v, double* red) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = wave_sum(v);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
   __syncthreads();
   if (lane == 0) red[wave] = v;
   __syncthreads();
-  float t = 0.0f;
+  double t = 0.0;
   for (int i = 0; i < nw; ++i) t += red[i];
   return t;
 }
 
 // nn.InstanceNorm2d defaults (extractor.py:36-39): per-(n,c) plane, biased variance, no affine.
-// One workgroup per plane; two-pass mean / variance (planes are L2-resident on the re-read).
+// One workgroup per plane; two-pass mean / variance (planes are L2-resident on the re-read).  The sums run in DOUBLE, as
+// instance_stats_finalize_kernel's do, and {mean, rstd} are rounded to float once: a float32 sum leaves an error of a few
+// 2^-24 of the plane's MAGNITUDE on the mean - of any size against a mean that is near zero by cancellation (26 x 2^-24
+// of it on a 12 x 43 plane of unit noise), which the single-pass route (statistics merged in double) does not have.  The
+// third pass is instance_norm_apply_kernel's expression, so the two routes differ by the rounding of their statistics alone.
 __global__ __launch_bounds__(512) void instance_norm_kernel(const float* x, const float* res,
                                                             float* out, int HW, float eps, int mode) {
-  __shared__ float red[8];
+  __shared__ double red[8];
   const long long base = (long long)blockIdx.x * HW;
   const float* p = x + base;
   const bool vec = (HW & 3) == 0;
-  float s = 0.0f;
+  double s = 0.0;
   if (vec) {
     const float4* p4 = reinterpret_cast<const float4*>(p);
     for (int i = threadIdx.x; i < HW / 4; i += blockDim.x) {
       const float4 v = p4[i];
-      s += (v.x + v.y) + (v.z + v.w);
+      s += ((double)v.x + (double)v.y) + ((double)v.z + (double)v.w);
     }
   } else {
-    for (int i = threadIdx.x; i < HW; i += blockDim.x) s += p[i];
+    for (int i = threadIdx.x; i < HW; i += blockDim.x) s += (double)p[i];
   }
-  const float mean = block_sum(s, red) / (float)HW;
-  float q = 0.0f;
+  const double mean_d = block_sum(s, red) / (double)HW;
+  double q = 0.0;
   if (vec) {
     const float4* p4 = reinterpret_cast<const float4*>(p);
     for (int i = threadIdx.x; i < HW / 4; i += blockDim.x) {
       const float4 v = p4[i];
-      const float a = v.x - mean, b = v.y - mean, c = v.z - mean, d = v.w - mean;
+      const double a = (double)v.x - mean_d, b = (double)v.y - mean_d, c = (double)v.z - mean_d, d = (double)v.w - mean_d;
       q += (a * a + b * b) + (c * c + d * d);
     }
   } else {
     for (int i = threadIdx.x; i < HW; i += blockDim.x) {
-      const float a = p[i] - mean;
+      const double a = (double)p[i] - mean_d;
       q += a * a;
     }
   }
-  const float var = block_sum(q, red) / (float)HW;
-  const float invstd = 1.0f / sqrtf(var + eps);
+  const double var = block_sum(q, red) / (double)HW;
+  const float mean = (float)mean_d, invstd = (float)(1.0 / sqrt(var + (double)eps));
   const float* r = res ? res + base : nullptr;
   float* o = out + base;
   for (int i = threadIdx.x; i < HW; i += blockDim.x) {

@@ -199,6 +199,14 @@ def test_c_abi_rejects_bad_arguments_without_a_gpu():
     # ... and so are the item indices of the gathered context split
     one = (ctypes.c_int * 1)(3)
     assert lib.accflow_split_tanh_relu_idx_f32(nz, 3, one, nz, 0, nz, 0, 1, 128, 128, 64, z) == 1
+    # the InstanceNorm statistics: a channel sub-range inside the statistics tensor, a positive slot count
+    eps = ctypes.c_float(1e-5)
+    for slots, ctot, c0 in ((4, 8, -1), (4, 8, 5), (0, 8, 0), (-3, 8, 0)):
+        assert lib.accflow_instance_stats_finalize_sub_f32(nz, slots, ctot, c0, nz, 1, 4, eps, z) == 1
+    # ... of the projected closing pass too (res_c0 + C > res_ctot; no statistics for the projection)
+    assert lib.accflow_instance_norm_apply_s16proj_f32(nz, nz, 4, nz, 128, nz, 4, 8, 5, nz, nz, 128, nz, 1, 4, 16, eps, z) == 1
+    assert lib.accflow_instance_norm_apply_s16proj_f32(nz, nz, 4, nz, 128, z, 4, 8, 0, nz, nz, 128, nz, 1, 4, 16, eps, z) == 1
+    assert lib.accflow_instance_norm_apply_f32(nz, nz, 4, nz, z, nz, 1, 4, 16, eps, 2, z) == 1     # mode 2 without a residual
     # sizes that are derivable without a device
     assert lib.accflow_conv_kpad(256, 3, 3) == 2304 and lib.accflow_conv_kpad(2, 7, 7) == 128
     assert lib.accflow_conv_coutpad(576) == 640
