@@ -833,6 +833,9 @@ int accflow_gma_aggregate_conv(const float* attnT, const float* v, const float* 
     if (!accflow_conv_direct_eligible(d)) return 1;
     return accflow_launch_conv_direct(d, D > 64 ? 2 : 1, st);
   }
+  // the im2col route packs v as split terms only: accflow_conv2d_f32 would hand <= 32 rows to the fp32 kernels, which read
+  // the pack as fp32 (the estimator's D is 128)
+  if (D <= 32) return 1;
   unsigned short* wsplit = reinterpret_cast<unsigned short*>(ws);
   int* ktab = reinterpret_cast<int*>(wsplit + 3LL * Kpad * CoutPad * B);
   float* wscale16 = reinterpret_cast<float*>(reinterpret_cast<char*>(ktab) + (long long)Kpad * 16);  // [B][CoutPad]

@@ -190,8 +190,10 @@ extern "C" int accflow_gma_attention_t_f32(const float* qk, float* attnT, void* 
   hipStream_t st = as_stream(stream);
   static const bool split_ok = [] { const char* e = getenv("ACCFLOW_GMA_QK_SPLIT"); return !e || atoi(e) != 0; }();
   // C[j][i] = scale * sum_d k[d][j] * q[d][i]: with scale = D^-1/2 (GMA's, modules.py:42) this is the correlation
-  // volume of (k, q), so the split modes reuse its matrix-core GEMM (bf16x6: fp32-equivalent) pair by pair
-  if (split_ok && mode != ACCFLOW_CONV_F32 && ws && fabsf(scale * sqrtf((float)D) - 1.0f) < 1e-6f) {
+  // volume of (k, q), so the split modes reuse its matrix-core GEMM (bf16x6: fp32-equivalent) pair by pair.
+  // P > 32: that GEMM is a convolution with P output rows, and accflow_conv2d_f32 gives <= 32 rows to the fp32 kernels, which
+  // read the weight pack as fp32 - level 0 writes only the split pack (the correlation volume never has fewer than 64 pixels)
+  if (split_ok && mode != ACCFLOW_CONV_F32 && ws && P > 32 && fabsf(scale * sqrtf((float)D) - 1.0f) < 1e-6f) {
     for (int b = 0; b < B; ++b) {
       const float* q = qk + (long long)b * 2 * D * P;
       const int rc = accflow_corr_level0_bf16s(q + (long long)D * P, q, attnT + (long long)b * P * P, ws, 1, D, H, W,

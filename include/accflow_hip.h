@@ -544,9 +544,11 @@ int accflow_gma_aggregate_f32(const float* attn, const float* v, const float* fm
  * hi + lo with per-row scales, guard as for accflow_conv_desc - or BF16X3/X6).
  * ws: accflow_gma_aggregate_ws_bytes(B, D, P) bytes.  Pairs out of the same image1 share their attention: a caller
  * stacks their v / fmap / out rows (D = n * 128) and passes B = 1 - one GEMM, the attention read once.
+ * accflow_gma_aggregate_t_f32 with D <= 32 rows: only the F16X3 single-item route (B = 1, P >= 16) has a kernel; every other
+ * combination returns 1 (the im2col kernels on the split packs need more than 32 output rows).
  * accflow_gma_attention_t_f32: P = H * W; in the split modes (mode != ACCFLOW_CONV_F32, ws = accflow_gma_attention_ws_bytes
- * bytes, scale = D^-1/2) the logits come from the correlation volume's matrix-core GEMM in its fp32-equivalent bf16x6
- * form, else (or ws NULL) from the fp32 MFMA GEMM; then a two-sweep column softmax. */
+ * bytes, scale = D^-1/2) and with P > 32 the logits come from the correlation volume's matrix-core GEMM in its
+ * fp32-equivalent bf16x6 form, else (or ws NULL, or P <= 32) from the fp32 MFMA GEMM; then a two-sweep column softmax. */
 long long accflow_gma_attention_ws_bytes(int D, int H, int W);
 /* Hot path in ACCFLOW_CONV_F16X3 (S16 format, see accflow_conv_desc): the attention of B feature maps, softmax over j,
  * stored j-major and PRE-SPLIT as an S16 tensor of P = H*W "channels" j over the H x W pixels i per item
