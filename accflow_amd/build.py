@@ -20,7 +20,7 @@ LIB = os.path.join(LIBDIR, "libaccflow_hip.so")
 SOURCES = ["conv2d_f32.hip", "conv2d_f32_v1.hip", "conv2d_f32_v2.hip", "conv2d_f32_v3.hip", "conv2d_bf16s.hip", "conv2d_bf16s_v12.hip", "conv2d_bf16s_v11.hip", "conv2d_bf16s_v21.hip",
            "conv2d_direct_v_bf16x6.hip", "conv2d_direct_v_bf16n.hip", "conv2d_direct_v_f16.hip", "conv2d_direct_v_s16.hip", "conv2d_direct_v_s16tg.hip", "conv2d_direct_v_s16k.hip", "conv2d_direct_v_s16k9.hip",
            "conv2d_direct_v_f16n.hip", "conv2d_direct_v_bf16x3.hip", "conv_s16m_v0.hip", "conv_s16m_v1.hip", "conv_s16m_v2.hip",
-           "conv_s16m_v3.hip", "conv2d_s16m.hip", "conv_stem.hip", "conv2d_direct.hip", "conv2d.hip", "corr_volume.hip",
+           "conv_s16m_v3.hip", "conv2d_s16m.hip", "conv_stem.hip", "conv2d_direct.hip", "conv2d.hip", "conv_plan.cpp", "corr_volume.hip",
            "corr_lookup.hip", "corr_disp.hip", "corr_alt.hip", "corr_lookup_conv.hip", "sampling.hip", "forward_interp.hip", "misc.hip", "gma.hip", "backward.hip"]
 ARCH = "gfx950"
 
@@ -75,11 +75,13 @@ def build(force=False, verbose=False, libdir=None, defines=(), unit_defines=()):
     objs = []
     for s in SOURCES:
         src = os.path.join(CSRC, s)
-        obj = os.path.join(objdir, s.replace(".hip", ".o"))
+        obj = os.path.join(objdir, os.path.splitext(s)[0] + ".o")
         objs.append(obj)
         extra = ["-D" + d for pre, d in unit_defines if s.startswith(pre)]
         if force or extra or not _newer(obj, sorted(_deps(src))):
-            jobs.append([cc] + flags + extra + ["-c", src, "-o", obj])
+            # (a .cpp unit is host code only - the convolution plan: plain C++, no offload pass)
+            lang = ["-x", "c++"] if s.endswith(".cpp") else []
+            jobs.append([cc] + lang + [f for f in flags if lang == [] or not f.startswith("--offload-arch")] + extra + ["-c", src, "-o", obj])
 
     def run(cmd):
         import time

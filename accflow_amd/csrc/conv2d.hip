@@ -629,11 +629,6 @@ __global__ void conv_ktab_kernel(int Cin, int Kpad, int4* __restrict__ ktab) {
   ktab[k] = e;
 }
 
-long long patch_min_blocks() {  // ACCFLOW_PATCH_MIN_BLOCKS=0 forces the patch kernel on small grids (tests)
-  static const long long v = [] { const char* e = getenv("ACCFLOW_PATCH_MIN_BLOCKS"); return e ? atoll(e) : 300LL; }();
-  return v;
-}
-
 }  // namespace
 
 
@@ -830,8 +825,9 @@ int accflow_gma_aggregate_conv(const float* attnT, const float* v, const float* 
     d.act = ACCFLOW_ACT_NONE; d.epi = ACCFLOW_EPI_ACCUM; d.e0 = fmap; d.e0_bs = (long long)D * P;
     d.wpatch = wpatch16; d.wpatch16 = wpatch16; d.wscale16 = wscale16; d.mode = mode; d.guard = guard;
     d.kws = kws; d.kws_elems = 8LL * D * P;
-    if (!accflow_conv_direct_eligible(d)) return 1;
-    return accflow_launch_conv_direct(d, D > 64 ? 2 : 1, st);
+    conv_plan p;
+    if (conv_plan_direct(d, D > 64 ? 2 : 1, false, p)) return 1;
+    return accflow_launch_conv_direct(d, p, st);
   }
   // the im2col route packs v as split terms only: accflow_conv2d_f32 would hand <= 32 rows to the fp32 kernels, which read
   // the pack as fp32 (the estimator's D is 128)
@@ -908,8 +904,9 @@ int accflow_gma_aggregate_s16_impl(const void* attn16, const float* v, const flo
   d.cb = D; d.out_cbs = out_bs; d.e0_cbs = fmap_bs; d.out16_cbs = out16_bs;
   d.wpatch = wpatch16; d.wpatch16 = wpatch16; d.wscale16 = wscale16; d.mode = ACCFLOW_CONV_F16X3; d.guard = guard;
   d.kws = kws; d.kws_elems = 8LL * Cout * P;
-  if (!accflow_conv_direct_eligible(d)) return 1;
-  return accflow_launch_conv_direct(d, Cout > 64 ? 2 : 1, st);
+  conv_plan p;
+  if (conv_plan_direct(d, Cout > 64 ? 2 : 1, false, p)) return 1;
+  return accflow_launch_conv_direct(d, p, st);
 }
 
 // GMA attention -> S16 (gma_attn_gemm_kernel, conv2d_direct.hip): q and k are packed as fp16 hi / lo of x * 2^ASHIFT (k
@@ -949,17 +946,6 @@ extern "C" int accflow_gma_attention_s16(const float* qk, void* attn16, void* ws
   ACCFLOW_RETURN_LAUNCH_STATUS();
 }
 
-extern "C" long long accflow_s16_item_words(int C, int H, int W) {
-  return (long long)((C + 7) / 8) * 2 * H * W * 4;   // octets x 2 terms x pixels x 16 bytes, in 4-byte words
-}
-
-extern "C" int accflow_conv_kpad(int Cin, int KH, int KW) {
-  const int K = Cin * KH * KW;
-  return (K + 31) / 32 * 32;  // multiple of every slab depth in use (16 and 32)
-}
-
-extern "C" int accflow_conv_coutpad(int Cout) { return (Cout + 127) / 128 * 128; }
-
 extern "C" int accflow_conv_pack_f32(const float* w, const float* scale, int Cout, int Cin, int KH, int KW,
                                      int C0, int tap_major, float* wpack, int* ktab, void* stream) {
   if (!w || !wpack || !ktab || Cout <= 0 || Cin <= 0 || KH <= 0 || KW <= 0) return 1;
@@ -984,229 +970,47 @@ extern "C" int accflow_conv_pack_all_f32(const float* w, const float* scale, int
   ACCFLOW_RETURN_LAUNCH_STATUS();
 }
 
-thread_local int* accflow_tls_dry_slots = nullptr;
-thread_local int* accflow_tls_dry_route = nullptr;
-
 extern "C" int accflow_conv_in_norm_supported(const accflow_conv_desc* desc) {
   if (!desc) return 0;
-  int slots = 0, route = 0;
-  accflow_conv_desc probe = *desc;
+  accflow_conv_desc probe = *desc, d;   // (asked before in_norm and stats exist: neither decides the route)
   probe.in_norm = nullptr;
   probe.stats = nullptr;
-  accflow_tls_dry_slots = &slots;
-  accflow_tls_dry_route = &route;
-  const int rc = accflow_conv2d_f32(&probe, nullptr);
-  accflow_tls_dry_slots = nullptr;
-  accflow_tls_dry_route = nullptr;
-  return rc ? 0 : route;
+  conv_plan p;
+  return !conv_validate(&probe, d) && !conv_make_plan(d, false, p) && p.can_norm ? 1 : 0;
 }
 
 extern "C" int accflow_conv_stat_slots(const accflow_conv_desc* desc) {
   if (!desc || desc->epi != ACCFLOW_EPI_STORE || desc->act != ACCFLOW_ACT_NONE) return 0;
-  int slots = 0;
-  accflow_tls_dry_slots = &slots;
-  const int rc = accflow_conv2d_f32(desc, nullptr);
-  accflow_tls_dry_slots = nullptr;
-  return rc ? 0 : slots;
-}
-
-bool accflow_conv_stem_eligible(const accflow_conv_desc& d);              // conv_stem.hip
-int accflow_launch_conv_stem(const accflow_conv_desc& d, hipStream_t st);
-
-// (the pre-split GRU state rides on the tap-specialised 5-tap instantiations: both A/B switches of that route must be on;
-// read once per process - Python asks this function instead of re-reading the switches, so the two cannot disagree)
-extern "C" int accflow_conv_gru16_supported(void) {
-  static const bool ok = [] {
-    const char* a = getenv("ACCFLOW_DIRECT_KT"); const char* b = getenv("ACCFLOW_DIRECT_W4"); const char* c = getenv("ACCFLOW_S16M");
-    return !(a && atoi(a) == 0) && !(b && atoi(b) == 0) && !(c && atoi(c) != 0);
-  }();
-  return ok ? 1 : 0;
+  accflow_conv_desc d;
+  conv_plan p;
+  return !conv_validate(desc, d) && !conv_make_plan(d, true, p) ? p.slots : 0;
 }
 
 extern "C" int accflow_conv2d_f32(const accflow_conv_desc* desc, void* stream) {
-  if (!desc) return 1;
-  accflow_conv_desc dd = *desc;
-  // the row / activation scales belong to the fp16 pack: every other kernel must not see them
-  if (dd.mode == ACCFLOW_CONV_F16X3 && (dd.wpatch16 || dd.wsplit16) && !dd.wscale16) return 1;
-  if (dd.mode != ACCFLOW_CONV_F16X3) { dd.wpatch16 = nullptr; dd.wsplit16 = nullptr; }
-  if (!dd.wpatch16 && !dd.wsplit16) dd.wscale16 = nullptr;
-  dd.acc_scale = 0.0f;
-  if (dd.nsrc < 0 || dd.nsrc > ACCFLOW_CONV_MAX_SRC) return 1;
-  // an S16 e0: the multi-source kernel's residual operand, or - round 6 - the GRU state of the 5-tap S16 direct convolutions on
-  // PACKED operands (accflow_conv_desc.p32): GRU_ZR with p32 = 3, GRU_Q with p32 = 6, whole 128-channel blocks, no split-K
-  const bool gru16 = !dd.nsrc && dd.e0_fmt;
-  if (gru16 && !(dd.in_fmt == (dd.in1 ? 3 : 1) && dd.e0 && dd.pre && dd.out16 && dd.mode == ACCFLOW_CONV_F16X3 && !dd.cb && !dd.kws &&
-                 dd.KH * dd.KW == 5 && dd.stride == 1 && accflow_conv_gru16_supported() && !dd.stats &&
-                 ((dd.epi == ACCFLOW_EPI_GRU_ZR && dd.p32 == 3 && dd.out && dd.Cout == 256) ||
-                  (dd.epi == ACCFLOW_EPI_GRU_Q && dd.p32 == 6 && dd.e1 && dd.Cout == 128))))
-    return 1;
-  // a pixel-major fp32 destination alone: a plain store of an S16-source direct convolution on whole 128-channel blocks
-  if (!gru16 && dd.p32 && !(dd.p32 == 1 && !dd.nsrc && dd.in_fmt == (dd.in1 ? 3 : 1) && dd.mode == ACCFLOW_CONV_F16X3 && dd.out && !dd.out16 &&
-                            dd.epi == ACCFLOW_EPI_STORE && (dd.act == ACCFLOW_ACT_NONE || dd.act == ACCFLOW_ACT_RELU) && !dd.cb &&
-                            !dd.kws && !dd.stats && dd.stride == 1 && (dd.Cout % 128) == 0 && accflow_conv_gru16_supported()))
-    return 1;
-  const bool multi = dd.nsrc > 0;   // multi-source S16 form: src[] replaces in0 / in1 and the conv geometry fields
-  if (multi) {
-    if (dd.mode != ACCFLOW_CONV_F16X3 || !dd.wpatch16 || dd.in_norm || dd.offset || dd.wsplit_bs) return 1;
-    dd.in_fmt = 0; dd.in0 = nullptr; dd.in1 = nullptr; dd.H = dd.OH; dd.W = dd.OW;
-    dd.CoutPad = accflow_conv_coutpad(dd.Cout);
-  }
-  const accflow_conv_desc& d = dd;
-  if ((!multi && (!d.in0 || !d.wpack || !d.ktab)) || d.B <= 0 || d.Cout <= 0 || d.OH <= 0 || d.OW <= 0) return 1;
-  if (d.epi == ACCFLOW_EPI_TAPGEMM) {   // the result feeds the tap matrix of a following small-Cout conv inside the kernel
-    if (multi || d.mode != ACCFLOW_CONV_F16X3 || !d.wpatch16 || !d.wscale16 || d.in_fmt != (d.in1 ? 3 : 1) || d.act != ACCFLOW_ACT_RELU ||
-        (d.Cout & 127) || d.kws || d.stats || d.in_norm || d.cb || d.pre || d.offset || !d.tg_w16 || !d.tg_scale || !d.tg_out ||
-        d.tg_rows < 1 || d.tg_rows > ACCFLOW_TAPGEMM_MAXROWS || d.tg_coutpad < 32 || (d.tg_coutpad & 31) ||
-        d.tg_out_bs < (long long)d.tg_rows * d.OH * d.OW || (d.Cout > 128 && d.tg_out_ps <= 0) || !accflow_conv_direct_eligible(d) ||
-        d.Kpad != accflow_conv_kpad(d.C0 + d.C1, d.KH, d.KW) || d.CoutPad != accflow_conv_coutpad(d.Cout))
-      return 1;
-    if ((((long long)(d.B - 1)) * d.in0_bs + accflow_s16_item_words(d.C0, d.H, d.W)) * 4 >= (1LL << 32)) return 1;
-    if (d.in1 && (((long long)(d.B - 1)) * d.in1_bs + accflow_s16_item_words(d.C1, d.H, d.W)) * 4 >= (1LL << 32)) return 1;
-    return accflow_launch_conv_direct(d, 2, as_stream(stream));
-  }
-  // the fp32 destination may be omitted only when the S16 copy is requested (GRU_ZR: that concerns out2 = r*h; z stays)
-  if (!d.out && (!d.out16 || d.epi == ACCFLOW_EPI_GRU_ZR)) return 1;
-  if (d.epi == ACCFLOW_EPI_GRU_ZR && !d.out2 && !d.out16) return 1;
-  if ((d.in_fmt || d.out16) && d.mode != ACCFLOW_CONV_F16X3) return 1;     // S16 tensors hold the fp16 split
-  if (d.in_fmt & ~3) return 1;
-  if (d.out16) {   // the S16 copy exists in the epilogue's specialised (epilogue, activation) forms only
-    const int ea = d.epi * 8 + d.act;
-    if (ea != ACCFLOW_EPI_STORE * 8 + ACCFLOW_ACT_NONE && ea != ACCFLOW_EPI_STORE * 8 + ACCFLOW_ACT_RELU &&
-        ea != ACCFLOW_EPI_STORE * 8 + ACCFLOW_ACT_SIGMOID && ea != ACCFLOW_EPI_RES_RELU * 8 + ACCFLOW_ACT_RELU &&
-        ea != ACCFLOW_EPI_RES_RELU * 8 + ACCFLOW_ACT_NONE &&
-        ea != ACCFLOW_EPI_GRU_ZR * 8 + ACCFLOW_ACT_SIGMOID && ea != ACCFLOW_EPI_GRU_Q * 8 + ACCFLOW_ACT_TANH &&
-        ea != ACCFLOW_EPI_ACCUM * 8 + ACCFLOW_ACT_NONE)
-      return 1;
-  }
-  if (d.cb && ((d.cb & 31) || (d.epi != ACCFLOW_EPI_STORE && d.epi != ACCFLOW_EPI_ACCUM) || d.stats || d.Cout % d.cb)) return 1;
-  if (!multi && (d.Kpad != accflow_conv_kpad(d.C0 + d.C1, d.KH, d.KW) || d.CoutPad != accflow_conv_coutpad(d.Cout))) return 1;
-  if ((d.epi == ACCFLOW_EPI_RES_RELU || d.epi == ACCFLOW_EPI_ACCUM) && !d.e0) return 1;
-  if (d.epi == ACCFLOW_EPI_GRU_ZR && (!d.e0 || (d.Cout & 1))) return 1;
-  if (d.epi == ACCFLOW_EPI_GRU_ZR && d.out16 && ((d.Cout >> 1) & 7)) return 1;
-  if (d.epi == ACCFLOW_EPI_GRU_Q && (!d.e0 || !d.e1)) return 1;
-  if (d.pre && d.epi != ACCFLOW_EPI_GRU_ZR && d.epi != ACCFLOW_EPI_GRU_Q) return 1;
-  if (d.offset && !d.dmask) return 1;
-  if ((long long)d.B * d.OH * d.OW >= (1LL << 31)) return 1;
-  // sources are addressed through 32-bit buffer offsets: each must span < 4 GiB (callers chunk the batch)
-  if (!multi) {
-    const long long w0 = (d.in_fmt & 1) ? accflow_s16_item_words(d.C0, d.H, d.W) : (long long)d.C0 * d.H * d.W;
-    const long long w1 = (d.in_fmt & 2) ? accflow_s16_item_words(d.C1, d.H, d.W) : (long long)d.C1 * d.H * d.W;
-    if ((((long long)(d.B - 1)) * d.in0_bs + w0) * 4 >= (1LL << 32)) return 1;
-    if (d.in1 && (((long long)(d.B - 1)) * d.in1_bs + w1) * 4 >= (1LL << 32)) return 1;
-  }
-  if (d.out16 && (((long long)(d.B - 1)) * d.out16_bs + accflow_s16_item_words(d.Cout, d.OH, d.OW)) * 4 >= (1LL << 32)) return 1;
-  if (d.stats && (d.epi != ACCFLOW_EPI_STORE || d.act != ACCFLOW_ACT_NONE || d.stat_slots <= 0)) return 1;
+  accflow_conv_desc d;
+  conv_plan p;
+  if (conv_validate(desc, d) || conv_make_plan(d, d.stats != nullptr, p)) return 1;
+  if (d.stats && p.slots != d.stat_slots) return 1;   // the route must be the one accflow_conv_stat_slots reported for
+  if (d.in_norm && !p.can_norm) return 1;
   hipStream_t st = as_stream(stream);
-  const long long Ptot = (long long)d.B * d.OH * d.OW;
-  if (d.in_norm && !accflow_tls_dry_slots && !accflow_conv_in_norm_supported(&d)) return 1;
-  if (d.stats && !accflow_tls_dry_slots) {  // the route must be the one accflow_conv_stat_slots reported for
-    int want = 0;
-    accflow_tls_dry_slots = &want;
-    accflow_conv_desc probe = d;
-    probe.stats = nullptr;
-    const int prc = accflow_conv2d_f32(&probe, nullptr);
-    accflow_tls_dry_slots = nullptr;
-    if (prc || want != d.stat_slots) return 1;
-  }
-  if (multi) return accflow_launch_conv_s16m(d, -1, st);
-  // the encoders' 7x7 stride-2 stem of the 3-channel image (conv_stem.hip; ACCFLOW_CONV_STEM=0: the im2col kernel, A/B)
-  static const bool stem_on = [] { const char* e = getenv("ACCFLOW_CONV_STEM"); return !e || atoi(e) != 0; }();
-  if (stem_on && accflow_conv_stem_eligible(d)) return accflow_launch_conv_stem(d, st);
-  // S16 sources of the in0 / in1 form: the direct kernel's S16 instantiations; ACCFLOW_S16M=1 sends them to the multi-source
-  // kernel instead (same results bit for bit; in the refinement loop it measured 2 - 6 % slower per launch on one box,
-  // profiles/r04_ab_s16m_vs_direct.txt, so the update block stays where it was)
-  static const bool s16m_on = [] { const char* e = getenv("ACCFLOW_S16M"); return e && atoi(e) != 0; }();
-  if (d.in_fmt && s16m_on) {
-    if (!accflow_conv_direct_eligible(d) || !d.wpatch16 || d.in_norm) return 1;
-    if (d.in_fmt != (d.in1 ? 3 : 1)) return 1;
-    accflow_conv_desc e = d;
-    accflow_s16m_from_legacy(e);
-    return accflow_launch_conv_s16m(e, -1, st);
-  }
-  if (d.in_fmt || d.out16 || d.cb) {
-    // S16 tensors exist for the direct kernel only: its DMA loader reads them, its epilogue writes them.  No diversion
-    // to another kernel whatever the grid size (the caller chose the format for this shape).
-    if (!accflow_conv_direct_eligible(d) || !d.wpatch16 || d.stats || d.in_norm) return 1;
-    if (d.in_fmt && d.in_fmt != (d.in1 ? 3 : 1)) return 1;
-    return accflow_launch_conv_direct(d, d.Cout > 64 ? 2 : 1, st);
-  }
-  if (d.Cout <= 4 && !d.offset && (d.epi == ACCFLOW_EPI_STORE || d.epi == ACCFLOW_EPI_ACCUM || d.epi == ACCFLOW_EPI_RES_RELU)) {
-    const bool same = d.stride == 1 && d.OH == d.H && d.OW == d.W && d.KH * d.KW >= 2 && d.C0 + d.C1 >= 16 &&
-                      (8 + d.KH - 1) * (16 + d.KW - 1) <= 192 && d.KH * d.KW <= 25 && (!d.in1 || d.C0 % 16 == 0);
-    ACCFLOW_DRY_RUN(0);
-    if (same) {
+  switch (p.family) {
+    case CONV_FAM_SMALL: {
+      dim3 grid(cdiv((long long)d.B * d.OH * d.OW, 64));
+      if (d.Cout <= 2) hipLaunchKernelGGL((conv2d_small_cout_kernel<2>), grid, dim3(256), 0, st, d);
+      else hipLaunchKernelGGL((conv2d_small_cout_kernel<4>), grid, dim3(256), 0, st, d);
+      ACCFLOW_RETURN_LAUNCH_STATUS();
+    }
+    case CONV_FAM_SMALL_PATCH: {
       dim3 pgrid((unsigned)((long long)d.B * cdiv(d.OW, 16) * cdiv(d.OH, 8)));
       if (d.Cout <= 2) hipLaunchKernelGGL((conv2d_small_cout_patch_kernel<2>), pgrid, dim3(256), 0, st, d);
       else hipLaunchKernelGGL((conv2d_small_cout_patch_kernel<4>), pgrid, dim3(256), 0, st, d);
       ACCFLOW_RETURN_LAUNCH_STATUS();
     }
-    dim3 grid(cdiv(Ptot, 64));
-    if (d.Cout <= 2) hipLaunchKernelGGL((conv2d_small_cout_kernel<2>), grid, dim3(256), 0, st, d);
-    else hipLaunchKernelGGL((conv2d_small_cout_kernel<4>), grid, dim3(256), 0, st, d);
-    ACCFLOW_RETURN_LAUNCH_STATUS();
+    case CONV_FAM_STEM: return accflow_launch_conv_stem(d, st);
+    case CONV_FAM_DIRECT: return accflow_launch_conv_direct(d, p, st);
+    case CONV_FAM_S16M: return accflow_launch_conv_s16m(d, p, st);
+    case CONV_FAM_IM2COL: return accflow_launch_conv_bf16s(d, p.tc, p.tp, p.Z, st);
+    case CONV_FAM_F32: return accflow_launch_conv_f32(d, p.wc, p.wp, p.tc, p.tp, st);
   }
-  if (accflow_conv_direct_eligible(d)) {
-    const long long nb = (long long)d.B * cdiv(d.OW, DIR_TW) * cdiv(d.OH, DIR_TH);
-    // with a split-K workspace small grids are split, not diverted (1x1 convolutions of < 512 channels: too few steps
-    // per part to pay)
-    const long long minb = (d.kws && (d.KH * d.KW >= 2 || d.C0 + d.C1 >= 512)) ? 0 : patch_min_blocks();
-    if (d.Cout > 64 && nb * cdiv(d.Cout, 128) >= minb) return accflow_launch_conv_direct(d, 2, st);  // 128 ch
-    if (nb * cdiv(d.Cout, 64) >= minb) return accflow_launch_conv_direct(d, 1, st);                  //  64 ch
-  }
-  // the im2col kernel's fp16 form needs its own pack; without it (per-batch weights, <= 32 output channels, deformable
-  // fp32 kernel, ...) the call runs bf16x6 arithmetic
-  if (d.mode == ACCFLOW_CONV_F16X3 && !(d.wsplit16 && !d.offset && d.Cout > 32)) {
-    accflow_conv_desc e = d;
-    e.mode = ACCFLOW_CONV_BF16X6;
-    e.wpatch = nullptr;       // (and must not come back here)
-    e.wpatch16 = nullptr; e.wsplit16 = nullptr; e.wscale16 = nullptr;
-    return accflow_conv2d_f32(&e, stream);
-  }
-  if (d.mode == ACCFLOW_CONV_F16X3 && d.wsplit_bs) {  // per-batch-item fp16 packs (+ per-item row scales): GMA aggregation
-    ACCFLOW_DRY_RUN(0);
-    if ((d.OH * d.OW) % 64) return 1;
-    return d.Cout > 64 ? accflow_launch_conv_bf16s(d, 2, 1, st) : accflow_launch_conv_bf16s(d, 1, 1, st);
-  }
-  if (d.mode == ACCFLOW_CONV_F16X3) {  // not direct-eligible (or too small a grid): im2col kernel on the fp16 pack
-    accflow_conv_desc e = d;
-    e.wpatch16 = nullptr;
-    auto nb = [&](int bc, int bp) { return (long long)cdiv(Ptot, bp) * cdiv(e.Cout, bc); };
-    if (e.Cout <= 64) return nb(64, 128) >= 384 ? accflow_launch_conv_bf16s(e, 1, 2, st) : accflow_launch_conv_bf16s(e, 1, 1, st);
-    if (nb(128, 128) >= 384) return accflow_launch_conv_bf16s(e, 2, 2, st);
-    if (nb(128, 64) >= 384) return accflow_launch_conv_bf16s(e, 2, 1, st);
-    return accflow_launch_conv_bf16s(e, 1, 1, st);
-  }
-  if (d.wsplit_bs) {  // per-batch-item weights: 64-pixel tiles that never straddle items
-    ACCFLOW_DRY_RUN(0);
-    if (d.mode == ACCFLOW_CONV_F32 || !d.wsplit || d.offset || ((d.OH * d.OW) % 64) || d.Cout <= 32) return 1;
-    return d.Cout > 64 ? accflow_launch_conv_bf16s(d, 2, 1, st) : accflow_launch_conv_bf16s(d, 1, 1, st);
-  }
-  if (d.mode != ACCFLOW_CONV_F32 && d.wsplit && !d.offset && d.Cout > 32) {
-    // split-bf16 matrix-core path (k order must be (c, tap): the tap-major pack is deformable-only)
-    auto nb = [&](int bc, int bp) { return (long long)cdiv(Ptot, bp) * cdiv(d.Cout, bc); };
-    if (d.Cout <= 64) return nb(64, 128) >= 384 ? accflow_launch_conv_bf16s(d, 1, 2, st) : accflow_launch_conv_bf16s(d, 1, 1, st);
-    // (a 192-channel x 128-pixel tile existed for Cout % 192 == 0 until round 5: the only such convolution of the workload,
-    // convc2, runs on the direct kernel; its instantiation group took 5.6 minutes to compile - the longest unit of the build)
-    if (nb(128, 128) >= 384) return accflow_launch_conv_bf16s(d, 2, 2, st);
-    if (nb(128, 64) >= 384) return accflow_launch_conv_bf16s(d, 2, 1, st);
-    return accflow_launch_conv_bf16s(d, 1, 1, st);
-  }
-  // Tile choice: the largest tile that still yields >= MIN_BLOCKS workgroups (256 CUs x ~1.5), since the
-  // fusion chain runs at batch 1 (7 680 pixels) where 128x128 tiles would leave most CUs idle.
-  ACCFLOW_DRY_RUN(0);  // (the fp32-MFMA kernels do not gather statistics)
-  constexpr long long MIN_BLOCKS = 384;
-  auto blocks = [&](int bc, int bp) { return (long long)cdiv(Ptot, bp) * cdiv(d.Cout, bc); };
-  if (d.Cout <= 32) {
-    if (blocks(32, 256) >= MIN_BLOCKS) return accflow_launch_conv_f32(d, 1, 4, 1, 2, st);   // 32 ch x 256 px
-    return accflow_launch_conv_f32(d, 1, 4, 1, 1, st);                                       // 32 ch x 128 px
-  }
-  if (d.Cout <= 64) {
-    if (blocks(64, 128) >= MIN_BLOCKS) return accflow_launch_conv_f32(d, 2, 2, 1, 2, st);   // 64 ch x 128 px
-    return accflow_launch_conv_f32(d, 2, 2, 1, 1, st);                                       // 64 ch x 64 px
-  }
-  if (d.Cout % 96 == 0 && d.Cout % 128 != 0 && blocks(96, 128) >= MIN_BLOCKS)
-    return accflow_launch_conv_f32(d, 1, 4, 3, 1, st);                                       // 96 ch x 128 px
-  if (blocks(128, 128) >= MIN_BLOCKS) return accflow_launch_conv_f32(d, 2, 2, 2, 2, st);    // 128 ch x 128 px
-  if (blocks(128, 64) >= MIN_BLOCKS) return accflow_launch_conv_f32(d, 2, 2, 2, 1, st);     // 128 ch x 64 px
-  return accflow_launch_conv_f32(d, 2, 2, 1, 1, st);                                         // 64 ch x 64 px
+  return 1;
 }

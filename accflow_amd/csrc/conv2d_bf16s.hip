@@ -1,11 +1,11 @@
 #include "conv2d_bf16s_kernel.h"
 
-int accflow_launch_conv_bf16s(const accflow_conv_desc& d, int tc, int tp, hipStream_t st) {
+int accflow_launch_conv_bf16s(const accflow_conv_desc& d, int tc, int tp, int Z, hipStream_t st) {
   switch (tc * 10 + tp) {
-    case 11: return accflow_launch_conv_bf16s_11(d, st);   //  64 ch x  64 px
-    case 12: return accflow_launch_conv_bf16s_12(d, st);   //  64 ch x 128 px
-    case 21: return accflow_launch_conv_bf16s_21(d, st);   // 128 ch x  64 px
-    case 22: return launch_conv_bf16s<2, 2>(d, st);        // 128 ch x 128 px (this translation unit)
+    case 11: return accflow_launch_conv_bf16s_11(d, Z, st);   //  64 ch x  64 px
+    case 12: return accflow_launch_conv_bf16s_12(d, Z, st);   //  64 ch x 128 px
+    case 21: return accflow_launch_conv_bf16s_21(d, Z, st);   // 128 ch x  64 px
+    case 22: return launch_conv_bf16s<2, 2>(d, Z, st);     // 128 ch x 128 px (this translation unit)
   }
   return 1;
 }

@@ -210,32 +210,11 @@ __global__ __launch_bounds__(256) void conv2d_bf16s_kernel(const accflow_conv_de
 template <int TC, int TP>
 int launch_conv_bf16s_grid(const accflow_conv_desc& d, dim3 grid, hipStream_t st);
 
+// Z: split-K parts (conv_plan.cpp)
 template <int TC, int TP>
-int launch_conv_bf16s(const accflow_conv_desc& d, hipStream_t st) {
+int launch_conv_bf16s(const accflow_conv_desc& d, int Z, hipStream_t st) {
   constexpr int BC = 2 * TC * 32, BP = 2 * TP * 32;
-  const long long Ptot = (long long)d.B * d.OH * d.OW;
-  // statistics: a pixel tile must not straddle two batch items; 2 waves along the pixels = 2 slots per tile
-  const int OHW = d.OH * d.OW;
-  ACCFLOW_DRY_RUN(OHW % BP == 0 ? OHW / BP * 2 : 0);
-  if (d.stats && OHW % BP) return 1;
-  dim3 grid(cdiv(Ptot, BP), cdiv(d.Cout, BC));
-  // split-K for deep reductions on grids that do not fill the 768 workgroup slots (3 per CU): the GMA aggregation
-  // (K = h*w = 14 400 at 720x1280, 225 pixel tiles per item).  The part count with the best fill of whole rounds wins.
-  int Z = 1;
-  const long long nout = Ptot * d.Cout;
-  if (d.kws && !d.stats && d.Kpad >= 2048 && (long long)grid.x * grid.y < 700) {
-    static const int zenv = [] { const char* e = getenv("ACCFLOW_IM2COL_KSPLIT"); return e ? atoi(e) : 0; }();
-    const long long nb = (long long)grid.x * grid.y;
-    double best = 0.0;
-    for (int z = 1; z <= 8; ++z) {
-      const double fill = (double)(nb * z) / (double)(cdiv(nb * z, 768) * 768);
-      if (fill > best + 0.03) { best = fill; Z = z; }
-    }
-    if (zenv > 0) Z = zenv;
-    if ((long long)Z * nout > d.kws_elems) Z = (int)(d.kws_elems / nout);
-    if (Z < 1) Z = 1;
-    grid.z = Z;
-  }
+  dim3 grid(cdiv((long long)d.B * d.OH * d.OW, BP), cdiv(d.Cout, BC), Z);
   const int rc = launch_conv_bf16s_grid<TC, TP>(d, grid, st);
   if (rc || Z == 1) return rc;
   return conv_ksplit_reduce_launch(d, Z, st);
@@ -266,6 +245,6 @@ int launch_conv_bf16s_grid(const accflow_conv_desc& d, dim3 grid, hipStream_t st
 
 }  // namespace
 
-int accflow_launch_conv_bf16s_11(const accflow_conv_desc& d, hipStream_t st);   //  64 ch x  64 px
-int accflow_launch_conv_bf16s_12(const accflow_conv_desc& d, hipStream_t st);   //  64 ch x 128 px
-int accflow_launch_conv_bf16s_21(const accflow_conv_desc& d, hipStream_t st);   // 128 ch x  64 px
+int accflow_launch_conv_bf16s_11(const accflow_conv_desc& d, int Z, hipStream_t st);   //  64 ch x  64 px
+int accflow_launch_conv_bf16s_12(const accflow_conv_desc& d, int Z, hipStream_t st);   //  64 ch x 128 px
+int accflow_launch_conv_bf16s_21(const accflow_conv_desc& d, int Z, hipStream_t st);   // 128 ch x  64 px

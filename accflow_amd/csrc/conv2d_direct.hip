@@ -233,68 +233,26 @@ int conv_ksplit_reduce_launch(const accflow_conv_desc& d, int Z, hipStream_t st)
 
 namespace {
 
-template <int TC>
-int launch_conv_direct(const accflow_conv_desc& d, hipStream_t st) {
+// one launch of the direct kernel as planned (conv_plan.cpp: tile, wave layout, loop variant, split-K parts)
+int launch_conv_direct(const accflow_conv_desc& d, const conv_plan& p, hipStream_t st) {
   const int tiles = cdiv(d.OW, DIR_TW) * cdiv(d.OH, DIR_TH);
-  const long long nb = (long long)d.B * tiles * cdiv(d.Cout, 2 * TC * 32);
-  // split-K for grids that leave most of the 256 CUs idle (the batch-1 fusion chain): 2-4 parts of >= 2 chunks
-  static const bool w4 = [] { const char* e = getenv("ACCFLOW_DIRECT_W4"); return !e || atoi(e) != 0; }();
-  // normalise-on-load (desc.in_norm): single-source input of <= 256 channels, the kernels instantiated for it
-  const bool norm_ok = !d.in1 && d.C0 <= DIR_NORM_MAXC && (TC == 1 || w4);
-  if (accflow_tls_dry_route) *accflow_tls_dry_route = norm_ok ? 1 : 0;
-  ACCFLOW_DRY_RUN(tiles * ((TC == 2 && w4) ? 1 : 2));  // one slot per wave along the pixels
-  if (d.in_norm && !norm_ok) return 1;
-  int Z = 1;
-  const long long nout = (long long)d.B * d.Cout * d.OH * d.OW;
-  const int nchunk = (d.C0 + d.C1 + 15) / 16;
-  if (d.kws && nchunk >= 256 && nb < 700 && !d.stats) {
-    // very deep reductions (GMA aggregation: 14 400 channels at 720x1280): the part count that best fills whole
-    // rounds of the 768 workgroup slots
-    static const int zenv = [] { const char* e = getenv("ACCFLOW_DIRECT_KSPLIT"); return e ? atoi(e) : 0; }();
-    double best = 0.0;
-    for (int z = 1; z <= 8; ++z) {
-      const double fill = (double)(nb * z) / (double)(cdiv(nb * z, 768) * 768);
-      if (fill > best + 0.03) { best = fill; Z = z; }
-    }
-    if (zenv > 0) Z = zenv;
-  } else if (d.kws && nb < 320 && !d.stats) {
-    // (a fill-based part count up to 8 here, too, measured no gain on the batch-1 fusion chain: 30.9 vs 31.0 ms)
-    Z = (int)((512 + nb - 1) / nb);
-    if (Z > 4) Z = 4;
-    if (Z > nchunk / 2) Z = nchunk / 2;
-  }
-  if (Z > 1 && (long long)Z * nout > d.kws_elems) Z = (int)(d.kws_elems / nout);
-  if (Z < 1) Z = 1;
-  if (d.out16 && d.epi == ACCFLOW_EPI_GRU_ZR && ((d.Cout >> 1) & 7)) Z = 1;
-  dim3 grid((unsigned)((long long)d.B * tiles), cdiv(d.Cout, 2 * TC * 32), Z);
-  // ACCFLOW_DIRECT_W4=0 selects the 2 x 2 wave layout of the 128-channel kernel (A/B measurements)
-  constexpr bool CAN_W4 = TC == 2;
-  const bool f16 = d.mode == ACCFLOW_CONV_F16X3 && d.wpatch16;
+  dim3 grid((unsigned)((long long)d.B * tiles), cdiv(d.Cout, 2 * p.tc * 32), p.Z);
+  const bool f16 = p.mode == ACCFLOW_CONV_F16X3 && d.wpatch16;
+  const int nt = p.mode == ACCFLOW_CONV_BF16X3 ? 2 : 3;
   int rc;
-  if (d.epi == ACCFLOW_EPI_TAPGEMM) {   // (validated by accflow_conv2d_f32)
-    if (TC != 2 || !f16 || !d.in_fmt || Z != 1 || !(CAN_W4 && w4)) return 1;
-    static const bool kt9_tg = [] { const char* e = getenv("ACCFLOW_DIRECT_KT9"); return !e || atoi(e) != 0; }();
-    rc = (kt9_tg && d.KH == 3 && d.KW == 3 && (d.C0 + d.C1) % 16 == 0) ? accflow_direct_launch_s16k9(d, 2, true, grid, st)
-                                                                        : accflow_direct_launch_s16tg(d, grid, st);
-  } else if (d.in_fmt) {  // S16 sources: the fp16 kernel with the DMA loader (every source must be S16; no normalise-on-load)
-    if (!f16 || d.in_norm || d.in_fmt != (d.in1 ? 3 : 1)) return 1;
-    // the tap-specialised K loop of the 128-channel kernel for 5-tap convolutions (the GRU's 1x5 / 5x1; ACCFLOW_DIRECT_KT=0: the
-    // generic loop, A/B runs): 23.80 / 23.72 vs 23.91 / 23.98 ms per step on one box
-    static const bool kt_on = [] { const char* e = getenv("ACCFLOW_DIRECT_KT"); return !e || atoi(e) != 0; }();
-    // ... and for 3x3 (9 taps; round 6, ACCFLOW_DIRECT_KT9=0: the generic loop): 23.27-23.31 vs 23.44-23.54 ms per step
-    static const bool kt9_on = [] { const char* e = getenv("ACCFLOW_DIRECT_KT9"); return !e || atoi(e) != 0; }();
-    if (kt_on && TC == 2 && CAN_W4 && w4 && d.KH * d.KW == 5) rc = accflow_direct_launch_s16k(d, 5, grid, st);
-    else if (kt9_on && (TC == 1 || (CAN_W4 && w4)) && d.KH == 3 && d.KW == 3) rc = accflow_direct_launch_s16k9(d, TC, false, grid, st);
-    else rc = accflow_direct_launch_s16(d, TC, grid, st);
-  } else if (d.in_norm) {
-    rc = f16 ? accflow_direct_launch_f16_norm(d, TC, grid, st)
-             : accflow_direct_launch_bf16_norm(d, TC, d.mode == ACCFLOW_CONV_BF16X3 ? 2 : 3, grid, st);
+  if (p.tapgemm) {
+    rc = p.loop == CONV_LOOP_TAP9 ? accflow_direct_launch_s16k9(d, 2, true, grid, st) : accflow_direct_launch_s16tg(d, grid, st);
+  } else if (d.in_fmt) {  // S16 sources: the fp16 kernel with the DMA loader
+    if (p.loop == CONV_LOOP_TAP5) rc = accflow_direct_launch_s16k(d, 5, grid, st);
+    else if (p.loop == CONV_LOOP_TAP9) rc = accflow_direct_launch_s16k9(d, p.tc, false, grid, st);
+    else rc = accflow_direct_launch_s16(d, p.tc, grid, st);
+  } else if (p.norm) {
+    rc = f16 ? accflow_direct_launch_f16_norm(d, p.tc, p.loop == CONV_LOOP_TAP9, grid, st) : accflow_direct_launch_bf16_norm(d, p.tc, nt, grid, st);
   } else {
-    rc = f16 ? accflow_direct_launch_f16(d, TC, CAN_W4 && w4, grid, st)
-             : accflow_direct_launch_bf16(d, TC, d.mode == ACCFLOW_CONV_BF16X3 ? 2 : 3, CAN_W4 && w4, grid, st);
+    rc = f16 ? accflow_direct_launch_f16(d, p.tc, p.w4, grid, st) : accflow_direct_launch_bf16(d, p.tc, nt, p.w4, grid, st);
   }
   if (rc) return rc;
-  if (Z > 1) return conv_ksplit_reduce_launch(d, Z, st);
+  if (p.Z > 1) return conv_ksplit_reduce_launch(d, p.Z, st);
   ACCFLOW_RETURN_LAUNCH_STATUS();
 }
 
@@ -725,40 +683,18 @@ int accflow_launch_corr_disp_direct(const accflow_conv_desc& d, hipStream_t st) 
   ACCFLOW_RETURN_LAUNCH_STATUS();
 }
 
-int accflow_launch_conv_direct(const accflow_conv_desc& d, int tc, hipStream_t st) {
-  // Cout = 128 m + 64 (convc2: 256 -> 192): with 128-channel workgroups only, the last channel block would run all its
-  // MFMAs with half of its rows on padding (25 % of the launch's matrix work wasted at 192).  Pointwise epilogues let
-  // the launch be cut in two along the channels: 128 m channels on the 128-channel kernel, the last 64 on the
-  // 64-channel kernel, through a descriptor whose channel-indexed pointers are advanced by ch0.
-  const bool pointwise = d.epi == ACCFLOW_EPI_STORE || d.epi == ACCFLOW_EPI_RES_RELU || d.epi == ACCFLOW_EPI_ACCUM;
-  if (tc == 2 && d.Cout > 128 && d.Cout % 128 > 0 && d.Cout % 128 <= 64 && pointwise && !d.stats && !accflow_tls_dry_slots && !(d.kws && (long long)d.B * cdiv(d.OW, DIR_TW) * cdiv(d.OH, DIR_TH) * cdiv(d.Cout, 128) < 320)) {
-    const int ch0 = d.Cout / 128 * 128;
-    const long long OHW = (long long)d.OH * d.OW;
-    accflow_conv_desc a = d, b = d;
-    a.Cout = ch0;
-    b.Cout = d.Cout - ch0;
-    b.out = d.out ? d.out + ch0 * OHW : nullptr;
-    if (d.bias) b.bias = d.bias + ch0;
-    if (d.wscale16) b.wscale16 = d.wscale16 + ch0;
-    if (d.e0) b.e0 = d.e0 + ch0 * OHW;
-    if (d.out16) b.out16 = reinterpret_cast<char*>(d.out16) + (long long)(ch0 / 8) * 2 * OHW * 16;
-    // packs are [term][step][octet][CoutPad][8]: the same CoutPad pitch, the channel origin moved by ch0 16-byte rows
-    if (d.wpatch) b.wpatch = reinterpret_cast<const char*>(d.wpatch) + (long long)ch0 * 16;
-    if (d.wpatch16) b.wpatch16 = reinterpret_cast<const char*>(d.wpatch16) + (long long)ch0 * 16;
-    const int rc = launch_conv_direct<2>(a, st);
+int accflow_launch_conv_direct(const accflow_conv_desc& d, const conv_plan& p, hipStream_t st) {
+  if (!p.ch0) return launch_conv_direct(d, p, st);
+  // Cout = 128 m + 64: the 128 m channels on the 128-channel kernel, the last 64 on the 64-channel kernel (conv_tail_ch0)
+  accflow_conv_desc part[2];
+  conv_tail_split(d, p.ch0, part[0], part[1]);
+  for (int i = 0; i < 2; ++i) {
+    conv_plan pp;
+    int rc = conv_plan_part(part[i], p, i == 1, pp);
+    if (!rc) rc = launch_conv_direct(part[i], pp, st);
     if (rc) return rc;
-    return launch_conv_direct<1>(b, st);
   }
-  return tc == 2 ? launch_conv_direct<2>(d, st) : launch_conv_direct<1>(d, st);
-}
-
-bool accflow_conv_direct_eligible(const accflow_conv_desc& d) {
-  if (!d.wpatch || d.wsplit_bs || d.mode == ACCFLOW_CONV_F32 || d.offset || d.stride != 1 || d.Cout <= 4) return false;
-  if (d.OH != d.H || d.OW != d.W) return false;                                // "same" convolutions only
-  if ((DIR_TH + d.KH - 1) * (DIR_TW + d.KW - 1) > DIR_NPMAX) return false;
-  if (d.C0 + d.C1 < 16) return false;                                          // 2 / 3-channel stems: im2col kernel
-  if (d.in1 && (d.C0 % (d.KH * d.KW == 1 ? 32 : 16))) return false;            // a chunk must not straddle the sources
-  return true;
+  return 0;
 }
 
 #ifdef ACCFLOW_KPROF

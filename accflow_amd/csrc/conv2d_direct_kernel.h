@@ -215,7 +215,6 @@ __device__ __forceinline__ void conv_epilogue_tapgemm(const accflow_conv_desc& d
 // plane, 0xFFFFFFFF in the zero padding, which the DMA writes as zeros; the plane rides in the scalar offset): no
 // gather into registers, no conversion, no LDS store instruction, 16 registers fewer.  Round 3's precision probe
 // (profiles/r03_precision_probe.txt) showed the kernel bound by exactly that staging work, not by the matrix pipe.
-constexpr int DIR_NORM_MAXC = 256;
 // PM: which of the fp16 split's three products run (bits as ACCFLOW_F16_PAIRMASK) - 7 in every product instantiation.  Round 5
 // instantiated PM = 6 / 5 / 4 for the GMA aggregation GEMM alone (its activation operand is the attention matrix: softmax
 // probabilities averaged over 14 400 targets): C5 EPE 6.1e-5 -> 4.8e-4 / 5.4e-4 / 7.0e-4 px for -2.7 ms of 80 - inside the 1e-3
@@ -704,6 +703,6 @@ int accflow_direct_launch_s16tg(const accflow_conv_desc& d, dim3 grid, hipStream
 int accflow_direct_launch_s16k9(const accflow_conv_desc& d, int tc, bool tapgemm, dim3 grid, hipStream_t st);   // 3x3 forms of the loop below
 int accflow_direct_launch_s16k(const accflow_conv_desc& d, int kt, dim3 grid, hipStream_t st);   // tap-specialised loop (KT = 5), 128-channel kernel
 int accflow_direct_launch_f16(const accflow_conv_desc& d, int tc, bool w4, dim3 grid, hipStream_t st);
-int accflow_direct_launch_f16_norm(const accflow_conv_desc& d, int tc, dim3 grid, hipStream_t st);
+int accflow_direct_launch_f16_norm(const accflow_conv_desc& d, int tc, bool kt9, dim3 grid, hipStream_t st);   // kt9: the 9-tap loop (128-channel kernel)
 int accflow_direct_launch_bf16(const accflow_conv_desc& d, int tc, int nt, bool w4, dim3 grid, hipStream_t st);
 int accflow_direct_launch_bf16_norm(const accflow_conv_desc& d, int tc, int nt, dim3 grid, hipStream_t st);

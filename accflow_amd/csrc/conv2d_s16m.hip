@@ -1,5 +1,5 @@
-// Host side of the multi-source S16 convolution kernel (conv_s16m_kernel.h): validation, wave-layout choice, split-K,
-// and its weight pack (accflow_conv_pack_multi16).
+// Host side of the multi-source S16 convolution kernel (conv_s16m_kernel.h): the launch of a plan (validation, wave-layout
+// choice and split-K: conv_plan.cpp) and its weight pack (accflow_conv_pack_multi16).
 #include "conv_s16m_kernel.h"
 
 namespace {
@@ -75,71 +75,20 @@ long long multi_steps(int nsrc, const int* C, const int* KH, const int* KW) {
   return n;
 }
 
-template <int TH>
-bool s16m_fits(const accflow_conv_desc& d) {
-  for (int s = 0; s < d.nsrc; ++s) {
-    const accflow_conv_src& S = d.src[s];
-    if ((TH + S.KH - 1) * (S16M_TW + S.KW - 1) > s16m_cap(TH) / 4) return false;
-  }
-  return true;
-}
-
-template <int LAY>
-int s16m_launch(const accflow_conv_desc& d, hipStream_t st) {
-  using L = s16m_lay<LAY>;
-  constexpr int BC = L::WC * L::TCW * 32;
-  const int tiles = cdiv(d.OW, S16M_TW) * cdiv(d.OH, L::TH);
-  const long long nb = (long long)d.B * tiles * cdiv(d.Cout, BC);
-  ACCFLOW_DRY_RUN(tiles * L::WP);  // one statistics slot per wave along the pixels
-  int nchunk = 0;
-  long long nstep = 0;
-  for (int s = 0; s < d.nsrc; ++s) {
-    const s16m_geom g = s16m_geometry<L::TH>(d.src[s]);
-    nchunk += g.nch;
-    nstep += (long long)g.n16 * g.T;
-  }
-  // split-K: the rules of launch_conv_direct (conv2d_direct.hip)
-  int Z = 1;
-  const long long nout = (long long)d.B * d.Cout * d.OH * d.OW;
-  if (d.kws && nchunk >= 256 && nb < 700 && !d.stats) {
-    double best = 0.0;
-    for (int z = 1; z <= 8; ++z) {
-      const double fill = (double)(nb * z) / (double)(cdiv(nb * z, 768) * 768);
-      if (fill > best + 0.03) { best = fill; Z = z; }
-    }
-  } else if (d.kws && nb < 320 && !d.stats) {
-    Z = (int)((512 + nb - 1) / nb);
-    if (Z > 4) Z = 4;
-    if (Z > nchunk / 2) Z = nchunk / 2;
-  }
-  if (Z > 1 && (long long)Z * nout > d.kws_elems) Z = (int)(d.kws_elems / nout);
-  if (Z < 1) Z = 1;
-  if (d.out16 && d.epi == ACCFLOW_EPI_GRU_ZR && ((d.Cout >> 1) & 7)) Z = 1;
-  if (d.e0_fmt) Z = 1;   // (the split-K reduce kernel reads an fp32 residual)
-  if (d.split_c0) Z = 1; // (two convolutions with their own reduction lengths and activations: the reduce kernel knows one)
-  if (d.e0_fmt && (d.Cout % (L::TCW * 32))) return 1;   // every wave's rows all present, or all absent
-  dim3 grid((unsigned)((long long)d.B * tiles), cdiv(d.Cout, BC), Z);
-  // the tap-specialised loop when every source is 3x3 / step 1 (ACCFLOW_S16M_KT9=0: the generic loop, A/B)
-  static const bool kt9_on = [] { const char* e = getenv("ACCFLOW_S16M_KT9"); return !e || atoi(e) != 0; }();
-  bool kt9 = kt9_on && !d.split_c0;
-  for (int s = 0; s < d.nsrc && kt9; ++s) kt9 = d.src[s].KH == 3 && d.src[s].KW == 3 && d.src[s].step == 1;
+// one launch of wave layout p.lay as planned (conv_plan.cpp)
+int s16m_launch(const accflow_conv_desc& d, const conv_plan& p, hipStream_t st) {
+  const s16m_layout& L = S16M_LAYOUTS[p.lay];
+  const int tiles = cdiv(d.OW, S16M_TW) * cdiv(d.OH, L.TH);
+  dim3 grid((unsigned)((long long)d.B * tiles), cdiv(d.Cout, L.WC * L.TCW * 32), p.Z);
+  const bool kt9 = p.loop == CONV_LOOP_TAP9;
   int rc;
-  if (LAY == 0) rc = accflow_s16m_launch_0(d, grid, st, kt9);
-  else if (LAY == 1) rc = accflow_s16m_launch_1(d, grid, st, kt9);
-  else if (LAY == 2) rc = accflow_s16m_launch_2(d, grid, st, kt9);
+  if (p.lay == 0) rc = accflow_s16m_launch_0(d, grid, st, kt9);
+  else if (p.lay == 1) rc = accflow_s16m_launch_1(d, grid, st, kt9);
+  else if (p.lay == 2) rc = accflow_s16m_launch_2(d, grid, st, kt9);
   else rc = accflow_s16m_launch_3(d, grid, st, kt9);
   if (rc) return rc;
-  if (Z > 1) return conv_ksplit_reduce_launch(d, Z, st);
+  if (p.Z > 1) return conv_ksplit_reduce_launch(d, p.Z, st);
   ACCFLOW_RETURN_LAUNCH_STATUS();
-}
-
-int s16m_launch_lay(const accflow_conv_desc& d, int lay, hipStream_t st) {
-  switch (lay) {
-    case 0: return s16m_launch<0>(d, st);
-    case 1: return s16m_launch<1>(d, st);
-    case 2: return s16m_launch<2>(d, st);
-    default: return s16m_launch<3>(d, st);
-  }
 }
 
 }  // namespace
@@ -175,89 +124,16 @@ extern "C" int accflow_conv_pack_multi16(const float* const* w, const float* sca
   ACCFLOW_RETURN_LAUNCH_STATUS();
 }
 
-// the in0 / in1 S16 form as sources (same pack: accflow_conv_pack_patch16's step order is (16-channel group, tap) over the
-// concatenated channels, and a chunk never straddles the two sources - C0 % 16 == 0, % 32 for 1x1)
-void accflow_s16m_from_legacy(accflow_conv_desc& e) {
-  e.nsrc = e.in1 ? 2 : 1;
-  for (int s = 0; s < e.nsrc; ++s) {
-    accflow_conv_src& S = e.src[s];
-    S.ptr = s ? (const void*)e.in1 : (const void*)e.in0;
-    S.bs = s ? e.in1_bs : e.in0_bs;
-    S.C = s ? e.C1 : e.C0;
-    S.Hs = e.H; S.Ws = e.W;
-    S.step = 1; S.oy = 0; S.ox = 0;
-    S.KH = e.KH; S.KW = e.KW; S.padH = e.padH; S.padW = e.padW;
-    S.reserved = 0;
-  }
-}
-
-bool accflow_conv_s16m_eligible(const accflow_conv_desc& d) {
-  if (d.nsrc < 1 || d.nsrc > ACCFLOW_CONV_MAX_SRC || !d.wpatch16 || !d.wscale16 || d.mode != ACCFLOW_CONV_F16X3) return false;
-  if (d.wsplit_bs || d.offset || d.in_norm || d.Cout <= 4) return false;
-  // an S16 residual operand exists in the lean residual epilogue only (every wave's 32 * TCW rows present)
-  if (d.e0_fmt && (d.epi != ACCFLOW_EPI_RES_RELU || d.act != ACCFLOW_ACT_RELU || d.cb || (d.Cout % 32) || !d.e0)) return false;
-  for (int s = 0; s < d.nsrc; ++s) {
-    const accflow_conv_src& S = d.src[s];
-    if (!S.ptr || S.C <= 0 || S.Hs <= 0 || S.Ws <= 0 || (S.step != 1 && S.step != 2) || S.KH <= 0 || S.KW <= 0) return false;
-    if (S.oy < 0 || S.ox < 0 || S.oy >= S.step || S.ox >= S.step) return false;
-    if (S.padH < 0 || S.padW < 0 || S.padH >= S.KH || S.padW >= S.KW) return false;
-    // 32-bit buffer offsets: each source must span < 4 GiB
-    if ((((long long)(d.B - 1)) * S.bs + accflow_s16_item_words(S.C, S.Hs, S.Ws)) * 4 >= (1LL << 32)) return false;
-    // a 1x1 source of the 4-octet chunk form ends on a 32-channel boundary unless it is the last (a chunk never straddles)
-  }
-  return s16m_fits<4>(d);
-}
-
-// lay < 0: automatic
-int accflow_launch_conv_s16m(const accflow_conv_desc& d, int lay, hipStream_t st) {
-  if (!accflow_conv_s16m_eligible(d)) return 1;
-  static const int env_lay = [] { const char* e = getenv("ACCFLOW_S16M_LAY"); return e ? atoi(e) : -1; }();
-  if (lay < 0 && d.src[0].reserved > 0) lay = d.src[0].reserved - 1;   // (tests / tuning: accflow_conv_src.reserved)
-  if (lay < 0) lay = env_lay;
-  const bool fits8 = s16m_fits<8>(d);
-  if (d.split_c0) {
-    // accflow_conv_desc.split_c0: the channel block must not straddle the two convolutions - 96 -> the 96-channel layout,
-    // 128 -> the 128-channel one, 64 -> a 64-channel one; both halves whole blocks (the lean epilogue, or the general one
-    // with act NONE for both: the InstanceNorm encoder's raw outputs + statistics)
-    const int c0 = d.split_c0, c1 = d.Cout - d.split_c0;
-    if (d.epi != ACCFLOW_EPI_STORE || d.cb || (d.act != ACCFLOW_ACT_NONE && (d.act != ACCFLOW_ACT_RELU || d.stats)) || c1 <= 0)
-      return 1;
-    int bc;
-    if (c0 == 96 && fits8) { lay = 3; bc = 96; }
-    else if (c0 == 128) { lay = 0; bc = 128; }
-    else if (c0 == 64) { lay = (fits8 && (long long)d.B * cdiv(d.OW, S16M_TW) * cdiv(d.OH, 8) >= 1536) ? 1 : 2; bc = 64; }
-    else return 1;
-    if (c1 % bc) return 1;
-    return s16m_launch_lay(d, lay, st);
-  }
-  const long long tiles8 = (long long)d.B * cdiv(d.OW, S16M_TW) * cdiv(d.OH, 8);
-  if ((lay == 1 || lay == 3) && !fits8) lay = -1;
-  if (lay >= 0 && lay <= 3) return s16m_launch_lay(d, lay, st);
-  // enough workgroups to fill the chip at 3 per CU
-  const bool big8 = fits8 && tiles8 >= 1536 && !(d.kws && tiles8 < 320);
-  if (d.Cout <= 64) return s16m_launch_lay(d, big8 ? 1 : 2, st);
-  // 96-channel blocks: 96 -> 96 (encoder layer2) and 192 = 2 x 96 (convc2: 212 vs 227 us as 128 + 64, profiles/r04_s16m_bench.txt)
-  if ((d.Cout <= 96 || d.Cout == 192) && fits8 && tiles8 >= 600 && !(d.kws && tiles8 < 320)) return s16m_launch_lay(d, 3, st);
-  // Cout = 128 m + 64 with a pointwise epilogue: 128 m channels on the 128-channel layout, the last 64 on a 64-channel one
-  // (accflow_launch_conv_direct's rule, conv2d_direct.hip)
-  const bool pointwise = d.epi == ACCFLOW_EPI_STORE || d.epi == ACCFLOW_EPI_RES_RELU || d.epi == ACCFLOW_EPI_ACCUM;
-  const long long tiles4 = (long long)d.B * cdiv(d.OW, S16M_TW) * cdiv(d.OH, 4);
-  if (d.Cout > 128 && d.Cout % 128 > 0 && d.Cout % 128 <= 64 && pointwise && !d.stats && !accflow_tls_dry_slots && !d.cb &&
-      !(d.kws && tiles4 * cdiv(d.Cout, 128) < 320)) {
-    const int ch0 = d.Cout / 128 * 128;
-    const long long OHW = (long long)d.OH * d.OW;
-    accflow_conv_desc a = d, b = d;
-    a.Cout = ch0;
-    b.Cout = d.Cout - ch0;
-    b.out = d.out ? d.out + ch0 * OHW : nullptr;
-    if (d.bias) b.bias = d.bias + ch0;
-    if (d.wscale16) b.wscale16 = d.wscale16 + ch0;
-    if (d.e0) b.e0 = d.e0 + ch0 * OHW;
-    if (d.out16) b.out16 = reinterpret_cast<char*>(d.out16) + (long long)(ch0 / 8) * 2 * OHW * 16;
-    b.wpatch16 = reinterpret_cast<const char*>(d.wpatch16) + (long long)ch0 * 16;
-    const int rc = s16m_launch_lay(a, 0, st);
+int accflow_launch_conv_s16m(const accflow_conv_desc& d, const conv_plan& p, hipStream_t st) {
+  if (!p.ch0) return s16m_launch(d, p, st);
+  // Cout = 128 m + 64: the 128 m channels on the 128-channel layout, the last 64 on a 64-channel one (conv_tail_ch0)
+  accflow_conv_desc part[2];
+  conv_tail_split(d, p.ch0, part[0], part[1]);
+  for (int i = 0; i < 2; ++i) {
+    conv_plan pp;
+    int rc = conv_plan_part(part[i], p, i == 1, pp);
+    if (!rc) rc = s16m_launch(part[i], pp, st);
     if (rc) return rc;
-    return s16m_launch_lay(b, 2, st);
   }
-  return s16m_launch_lay(d, 0, st);
+  return 0;
 }

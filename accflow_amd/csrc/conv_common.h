@@ -1,43 +1,32 @@
-// Device code shared by the convolution translation units (conv2d.hip: C-ABI, dispatch, packing, small-Cout kernels;
+// Device code shared by the convolution translation units (conv2d.hip: C-ABI, packing, small-Cout kernels;
 // conv2d_f32.hip: fp32-MFMA im2col kernel; conv2d_bf16s.hip: split-bf16 im2col kernel + displaced correlation store;
-// conv2d_direct.hip: split-bf16 direct-A patch kernel).  Everything here is internal linkage.
+// conv2d_direct.hip: split-bf16 direct-A patch kernel).  Everything here is internal linkage.  The dispatch itself is host
+// code without a HIP header: conv_plan.h / conv_plan.cpp, on the tile constants of conv_tiles.h.
 #pragma once
 #include "common.h"
 #include <stdlib.h>
+#include "conv_plan.h"
 
+// Dispatch: conv_plan.cpp turns a validated descriptor into a conv_plan (kernel family, tile, loop variant, split-K parts,
+// statistic slots); the launchers below execute a plan - they keep the grid arithmetic and the choice of the instantiation.
 // launch entry points of the kernel families (one translation unit each, so that they compile in parallel)
 int accflow_launch_conv_f32(const accflow_conv_desc& d, int wc, int wp, int tc, int tp, hipStream_t st);
-int accflow_launch_conv_bf16s(const accflow_conv_desc& d, int tc, int tp, hipStream_t st);
+int accflow_launch_conv_bf16s(const accflow_conv_desc& d, int tc, int tp, int Z, hipStream_t st);
 int conv_ksplit_reduce_launch(const accflow_conv_desc& d, int Z, hipStream_t st);  // conv2d_direct.hip
 int accflow_launch_corr_disp_bf16s(const accflow_conv_desc& d, hipStream_t st);
 int accflow_launch_corr_disp_direct(const accflow_conv_desc& d, hipStream_t st);
-int accflow_launch_conv_direct(const accflow_conv_desc& d, int tc, hipStream_t st);
-bool accflow_conv_direct_eligible(const accflow_conv_desc& d);
-// multi-source S16 kernel (conv2d_s16m.hip): lay < 0 = automatic wave layout
-int accflow_launch_conv_s16m(const accflow_conv_desc& d, int lay, hipStream_t st);
-void accflow_s16m_from_legacy(accflow_conv_desc& e);   // in0 / in1 S16 form -> src[]
-// accflow_conv_stat_slots() runs the dispatcher in a dry mode (call-scoped, per host thread): a launcher that sees the
-// pointer set reports how many statistic slots per plane its kernel would write (0: none) instead of launching
-extern thread_local int* accflow_tls_dry_slots;
-extern thread_local int* accflow_tls_dry_route;  // same protocol: 1 = direct kernel that can normalise on load
-#define ACCFLOW_DRY_RUN(SLOTS)                                 \
-  do {                                                         \
-    if (accflow_tls_dry_slots) {                               \
-      *accflow_tls_dry_slots = (SLOTS);                        \
-      return 0;                                                \
-    }                                                          \
-  } while (0)
+int accflow_launch_conv_direct(const accflow_conv_desc& d, const conv_plan& p, hipStream_t st);
+int accflow_launch_conv_s16m(const accflow_conv_desc& d, const conv_plan& p, hipStream_t st);   // multi-source S16 kernel (conv2d_s16m.hip)
+int accflow_launch_conv_stem(const accflow_conv_desc& d, hipStream_t st);                        // conv_stem.hip
 #ifndef ACCFLOW_EPI_GRU_AHEAD
 #define ACCFLOW_EPI_GRU_AHEAD 3     // (1 = round 1-5 behaviour; 4 spills 5 registers and costs 6 % conv rate: profiles/r06_ab_gru_epilogue_prefetch.txt)
 #endif
-constexpr int ACCFLOW_TAPGEMM_MAXROWS = 18;   // ACCFLOW_EPI_TAPGEMM: rows of the second product (3x3 taps x 2 channels)
 #ifndef ACCFLOW_CONV_XCD_ORDER
 #define ACCFLOW_CONV_XCD_ORDER 1   // (0: measurement builds - the plain launch order of rounds 1-5)
 #endif
 #ifndef ACCFLOW_CONV_XCD_MIN_K
 #define ACCFLOW_CONV_XCD_MIN_K 8192  // reduction depth from which the direct kernel reorders its launch index (conv2d_direct_kernel.h)
 #endif
-constexpr int DIR_TH = 4, DIR_TW = 32, DIR_NPMAX = 256;  // direct kernel: tile and max patch pixels (3x3: 204, 1x5: 144, 5x1: 256)
 
 namespace {
 

@@ -26,18 +26,7 @@
 
 namespace {
 
-template <int LAY> struct s16m_lay;
-template <> struct s16m_lay<0> { static constexpr int WC = 4, WP = 1, TCW = 1, TP = 4, TH = 4; };  // 128 ch x 128 px
-template <> struct s16m_lay<1> { static constexpr int WC = 2, WP = 2, TCW = 1, TP = 4, TH = 8; };  //  64 ch x 256 px
-template <> struct s16m_lay<2> { static constexpr int WC = 2, WP = 2, TCW = 1, TP = 2, TH = 4; };  //  64 ch x 128 px
-template <> struct s16m_lay<3> { static constexpr int WC = 1, WP = 4, TCW = 3, TP = 2, TH = 8; };  //  96 ch x 256 px
-// (A 128 ch x 256 px layout - WC 4, TP 8: every A fragment feeds 8 pixel tiles instead of 4 - was built after ablation
-// builds, tools/s16m_ablation.sh / profiles/r04_s16m_ablation.txt, showed the A stream from L2 to be the second largest
-// cost of the loop after the MFMAs: -19 % kernel time without it, -3 % with half the LDS reads.  Its 128 accumulator
-// registers leave 2 waves per SIMD, and it measured 3 - 6 % SLOWER than layout 0 on every update-block shape
-// (profiles/r04_s16m_bench.txt keeps the column); removed again.)
-
-constexpr int S16M_TW = 32;
+// (wave layouts s16m_lay<LAY>, S16M_TW, s16m_cap and the per-source geometry: conv_tiles.h - the host-side plan shares them)
 // ablation switches of experiment builds (tools/s16m_ablation.sh): what bounds the loop?  The product build has them all 0.
 #ifndef S16M_ABL_NOA
 #define S16M_ABL_NOA 0
@@ -59,29 +48,6 @@ constexpr int S16M_TW = 32;
 #ifndef S16M_LEAN_EPILOGUE
 #define S16M_LEAN_EPILOGUE 1   // (0: always the general epilogue - A/B builds)
 #endif
-// 16-byte chunks of one LDS stage: [2 terms][oc octets][pitch] with oc * pitch = S16M_CAP / 2
-__host__ __device__ constexpr int s16m_cap(int TH) { return TH == 4 ? 1024 : 1536; }
-
-// per-source quantities both sides of the pipeline derive from the descriptor
-struct s16m_geom {
-  int PW, NP, T, KW, oc, NPS, nch, nq, n16;
-};
-template <int TH>
-__host__ __device__ __forceinline__ s16m_geom s16m_geometry(const accflow_conv_src& S) {
-  s16m_geom g;
-  g.PW = S16M_TW + S.KW - 1;
-  g.NP = (TH + S.KH - 1) * g.PW;
-  g.T = S.KH * S.KW;
-  g.KW = S.KW;
-  g.nq = (g.NP + 63) >> 6;
-  // 1x1 sub-kernels stage 4 octets per chunk when the patch is small enough (two 16-deep steps per barrier)
-  g.oc = (g.T == 1 && g.nq * 64 * 8 <= s16m_cap(TH)) ? 4 : 2;
-  g.NPS = s16m_cap(TH) / (2 * g.oc);
-  g.n16 = (S.C + 15) >> 4;                        // 16-channel groups = steps per tap (the pack's step count: n16 * T)
-  g.nch = (g.n16 + (g.oc >> 1) - 1) / (g.oc >> 1);  // (the last chunk of a 4-octet source may hold one group only)
-  return g;
-}
-
 // Source s of the descriptor, read from the KERNARG segment with scalar loads.  Indexing d.src[] with a run-time s would make
 // hipcc keep a private copy of the whole by-value descriptor in scratch memory (672 bytes per lane, every access a scratch
 // load); the descriptor is the kernel's only argument, so src[] sits at offsetof(accflow_conv_desc, src) of the segment.

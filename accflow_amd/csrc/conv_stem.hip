@@ -15,7 +15,7 @@
 
 namespace {
 
-constexpr int ST_TH = 4, ST_TW = 32, ST_PH = 13, ST_PWH = 36;   // patch: 13 rows x 2 parities x 36 (35 / 34 used) columns
+constexpr int ST_PH = 13, ST_PWH = 36;   // patch: 13 rows x 2 parities x 36 (35 / 34 used) columns of a ST_TH x ST_TW tile (conv_tiles.h)
 constexpr int ST_K = 147, ST_STEPS = 10;
 
 constexpr int ST_PWORDS = 3 * ST_PH * 2 * ST_PWH;               // patch words; word ST_PWORDS.. : zeros for the padded k (147..159)
@@ -144,15 +144,8 @@ __global__ __launch_bounds__(256, ACCFLOW_STEM_WAVES) void conv_stem7_kernel(con
 
 }  // namespace
 
-bool accflow_conv_stem_eligible(const accflow_conv_desc& d) {
-  return d.mode == ACCFLOW_CONV_F16X3 && d.wsplit16 && d.wscale16 && !d.in1 && !d.in_fmt && !d.nsrc && d.C0 == 3 && d.KH == 7 &&
-         d.KW == 7 && d.stride == 2 && d.padH == 3 && d.padW == 3 && d.Cout > 32 && d.Cout <= 64 && !d.offset && !d.in_norm &&
-         !d.wsplit_bs && !d.cb && d.Kpad == 160 && d.OH == (d.H + 6 - 7) / 2 + 1 && d.OW == (d.W + 6 - 7) / 2 + 1;
-}
-
-int accflow_launch_conv_stem(const accflow_conv_desc& d, hipStream_t st) {
+int accflow_launch_conv_stem(const accflow_conv_desc& d, hipStream_t st) {   // (eligibility: conv_plan.cpp)
   const int tiles = cdiv(d.OW, ST_TW) * cdiv(d.OH, ST_TH);
-  ACCFLOW_DRY_RUN(tiles * 2);   // one statistics slot per wave along the pixels (WP = 2)
   hipLaunchKernelGGL(conv_stem7_kernel, dim3((unsigned)((long long)d.B * tiles)), dim3(256), 0, st, d);
   ACCFLOW_RETURN_LAUNCH_STATUS();
 }

@@ -173,7 +173,7 @@ def test_host_thresholds_are_the_ones_restated_here():
         return open(os.path.join(ROOT, *p)).read()
     csrc = ("accflow_amd", "csrc")
     assert "#define ACCFLOW_F16_ASHIFT %d\n" % ASHIFT in src("include", "accflow_hip.h")
-    assert "constexpr int DIR_TH = 4, DIR_TW = 32," in src(*csrc, "conv_common.h")
+    assert "constexpr int DIR_TH = 4, DIR_TW = 32," in src(*csrc, "conv_tiles.h")
     gma = src(*csrc, "gma.hip")
     assert "if (split_ok && mode != ACCFLOW_CONV_F32 && ws && P > 32 && fabsf(scale * sqrtf((float)D) - 1.0f) < 1e-6f) {" in gma
     assert "ACCFLOW_CONV_BF16X6, 0, nullptr, st, nullptr, nullptr);" in gma            # the split route is bf16x6 in every mode
@@ -187,28 +187,34 @@ def test_host_thresholds_are_the_ones_restated_here():
     assert "const bool f16 = mode == ACCFLOW_CONV_F16X3 && (P % 64) == 0;" in conv
     assert "if (mode == ACCFLOW_CONV_F16X3 && !f16) mode = ACCFLOW_CONV_BF16X6;" in conv
     assert "if (P % 64 == 0) {" in conv and "if (D <= 32) return 1;" in conv
-    assert "return accflow_launch_conv_direct(d, D > 64 ? 2 : 1, st);" in conv
-    assert "return accflow_launch_conv_direct(d, Cout > 64 ? 2 : 1, st);" in conv
+    assert "if (conv_plan_direct(d, D > 64 ? 2 : 1, false, p)) return 1;" in conv
+    assert "if (conv_plan_direct(d, Cout > 64 ? 2 : 1, false, p)) return 1;" in conv
+    assert conv.count("return accflow_launch_conv_direct(d, p, st);") == 3
     assert "d.kws = kws; d.kws_elems = 8LL * D * P;" in conv and "d.kws = kws; d.kws_elems = 8LL * Cout * P;" in conv
     assert "if (B == 1) { d.kws = kws; d.kws_elems = 8LL * D * P; }" in conv
     assert "constexpr int ROWS16_REG = %d;" % ROWS16_REG in conv
     assert "const bool inreg = nchunk <= ROWS16_REG * 256 && !(Cin & 3);" in conv
-    assert "return (K + 31) / 32 * 32;" in conv
-    assert "return d.Cout > 64 ? accflow_launch_conv_bf16s(d, 2, 1, st) : accflow_launch_conv_bf16s(d, 1, 1, st);" in conv
-    direct = src(*csrc, "conv2d_direct.hip")
-    assert "const int nchunk = (d.C0 + d.C1 + 15) / 16;" in direct
-    assert "if (d.kws && nchunk >= 256 && nb < 700 && !d.stats) {" in direct
-    assert "} else if (d.kws && nb < 320 && !d.stats) {" in direct
+    # the routing thresholds have one home, the plan unit: one split-K rule and one tail-split rule for every kernel family
+    plan = src(*csrc, "conv_plan.cpp")
+    assert "return (K + 31) / 32 * 32;" in plan
+    assert "return plan_im2col(d, d.Cout > 64 ? 2 : 1, 1, want_stats, true, p);" in plan     # per-item packs: 64-pixel tiles
+    assert "const int nchunk = (d.C0 + d.C1 + 15) / 16;" in plan
+    assert "p.Z = conv_split_k(d, want_stats, nb, nchunk >= 256, sw.direct_ksplit, nchunk);" in plan
+    assert "p.Z = conv_split_k(d, want_stats, nb, d.Kpad >= 2048, conv_switches_get().im2col_ksplit, 0);" in plan
+    assert "if (!d.kws || want_stats || d.e0_fmt || d.split_c0) return 1;" in plan
+    assert "if (deep && nb < 700) {" in plan and "} else if (nchunk > 0 && nb < 320) {" in plan
     for line in ("Z = (int)((512 + nb - 1) / nb);", "if (Z > 4) Z = 4;", "if (Z > nchunk / 2) Z = nchunk / 2;",
                  "if (Z > 1 && (long long)Z * nout > d.kws_elems) Z = (int)(d.kws_elems / nout);",
-                 "const long long nb = (long long)d.B * tiles * cdiv(d.Cout, 2 * TC * 32);"):
-        assert line in direct, line
-    assert "d.Cout > 128 && d.Cout % 128 > 0 && d.Cout % 128 <= 64 && pointwise" in direct
-    assert "cdiv(d.OH, DIR_TH) * cdiv(d.Cout, 128) < 320)) {" in direct
+                 "const long long nb = (long long)d.B * tiles * cdiv(d.Cout, 2 * tc * 32);",
+                 "const long long nb = (long long)cdiv((long long)d.B * OHW, BP) * cdiv(d.Cout, 2 * tc * 32);"):
+        assert line in plan, line
+    assert "if (d.Cout > 128 && d.Cout % 128 > 0 && d.Cout % 128 <= 64 && pointwise && !want_stats && !d.cb && !(d.kws && nb128 < 320))" in plan
+    assert "(long long)d.B * cdiv(d.OW, DIR_TW) * cdiv(d.OH, DIR_TH) * cdiv(d.Cout, 128));" in plan
+    assert plan.count("if (fill > best + 0.03) { best = fill; Z = z; }") == 1
+    direct = src(*csrc, "conv2d_direct.hip")
     bf = src(*csrc, "conv2d_bf16s_kernel.h")
-    assert "if (d.kws && !d.stats && d.Kpad >= 2048 && (long long)grid.x * grid.y < 700) {" in bf
-    assert bf.count("if (fill > best + 0.03) { best = fill; Z = z; }") == 1 == direct.count("if (fill > best + 0.03) { best = fill; Z = z; }")
-    assert "if ((long long)Z * nout > d.kws_elems) Z = (int)(d.kws_elems / nout);" in bf
+    for text in (conv, direct, bf, src(*csrc, "conv2d_s16m.hip")):       # ... and no launcher decides any of it again
+        assert "fill > best" not in text and "< 320" not in text and "< 700" not in text and "getenv(\"ACCFLOW_DIRECT" not in text
     # the products the split kernels keep: a = weights, b = activations, terms (2,0) (0,2) (1,1) only with three terms
     for line in ("c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2][tc], b[0][tp], c, 0, 0, 0);",
                  "c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][tc], b[2][tp], c, 0, 0, 0);",

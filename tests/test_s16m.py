@@ -294,6 +294,36 @@ def test_statistics_of_an_s16_convolution(ops, lay):
     assert float((got.cpu() - want).abs().max()) <= 2e-5
 
 
+@pytest.mark.parametrize("route", ["multi", "direct"])
+def test_statistics_of_a_192_channel_convolution(ops, route):
+    """Cout = 128 + 64 with a plain store is the shape a launch WITHOUT statistics cuts in two along the channels (128 on the
+    128-channel tile, 64 on a 64-channel one): with statistics it must run as the one launch whose slot count
+    accflow_conv_stat_slots reported (csrc/conv_plan.cpp, want_stats).  Ragged tiles both ways, through the multi-source
+    form and - fp32 input - through the direct kernel; output against the float64 convolution, statistics through the norm
+    applied from them, within the bounds of the tests above."""
+    g = gen(23)
+    B, Cin, Cout, H, W = 2, 32, 192, 9, 40
+    x = torch.randn(B, Cin, H, W, generator=g)
+    w = torch.randn(Cout, Cin, 3, 3, generator=g) * 0.05
+    b = torch.randn(Cout, generator=g) * 0.1
+    y = F.conv2d(x.double(), w.double(), b.double(), padding=1)
+    want = torch.relu(F.instance_norm(y, eps=1e-5)).float()
+    if route == "multi":
+        pk = ops.PackedMulti.from_cat(dev(w), dev(b), [Cin], 1)
+        got, st = ops.conv2d_multi(pk, [ops.to_s16(dev(x))], want_stats=True)
+    else:
+        got, st = ops.conv2d(ops.PackedConv(dev(w), dev(b), padding=1), dev(x), want_stats=True)
+    assert st is not None
+    err = rel_err(got.cpu(), y.float())
+    print("192-channel statistics case, %s: output rel_err %.3g (bound %.3g)" % (route, err, tol(Cin * 9)))
+    assert err <= tol(Cin * 9)
+    ops.instance_norm(got, 1, stats=st)
+    nerr = float((got.cpu() - want).abs().max())
+    print("192-channel statistics case, %s: normalised output max error %.3g (bound 2e-5)" % (route, nerr))
+    assert nerr <= 2e-5
+    assert not ops.guard_tripped()
+
+
 def test_split_k_and_residual_epilogues(ops):
     """Batch-1 launches (the fusion chain) split the reduction over the sources' chunks; residual / accumulate epilogues."""
     g = gen(15)
