@@ -946,6 +946,36 @@ extern "C" int accflow_gma_attention_s16(const float* qk, void* attn16, void* ws
   ACCFLOW_RETURN_LAUNCH_STATUS();
 }
 
+// alternate_attention (gma_alt.hip): the same two packs per item, pass 0 and the final statistics - and no matrix.  kpack /
+// qpack: B packs of 2 * (D / 8) * coutpad(P) * 16 bytes each, stats: (B, P, 2) = {max_i, 1 / sum_i}; ws (partial
+// statistics, accflow_gma_attention_alt_ws_bytes) is free again when the call's kernels have run.
+int accflow_launch_gma_attn_stats(const void* kpack, const void* qpack, float* part, float* stats, float acc_scale, int P, int D,
+                                  int Ppad, hipStream_t st);
+
+extern "C" int accflow_gma_attention_alt(const float* qk, void* kpack, void* qpack, float* stats, void* ws, int* guard, int B,
+                                         int D, int H, int W, float scale, void* stream) {
+  if (!qk || !kpack || !qpack || !stats || !ws || B <= 0 || D != 128 || H <= 0 || W <= 0) return 1;
+  if ((long long)H * W * 512 >= (1LL << 31) - 65536) return 1;   // 32-bit offsets inside one pack (gma_alt_aggregate_kernel)
+  const int P = H * W, Ppad = accflow_conv_coutpad(P), Kpad = accflow_conv_kpad(D, 1, 1);
+  hipStream_t st = as_stream(stream);
+  const long long pack_bytes = 2LL * (D / 8) * Ppad * 16;
+  const float fs = ldexpf(1.0f, ACCFLOW_F16_ASHIFT);
+  const long long n8 = (long long)(Kpad / 8) * Ppad;
+  for (int b = 0; b < B; ++b) {
+    const float* q = qk + (long long)b * 2 * D * P;
+    char* kp = reinterpret_cast<char*>(kpack) + b * pack_bytes;
+    char* qp = reinterpret_cast<char*>(qpack) + b * pack_bytes;
+    hipLaunchKernelGGL(conv_pack_kmajor_kernel, dim3(cdiv(n8, 256)), dim3(256), 0, st, q + (long long)D * P, P, D, Kpad, Ppad,
+                       reinterpret_cast<u32x4*>(kp), scale * fs, 1, guard);
+    hipLaunchKernelGGL(conv_pack_kmajor_kernel, dim3(cdiv(n8, 256)), dim3(256), 0, st, q, P, D, Kpad, Ppad,
+                       reinterpret_cast<u32x4*>(qp), fs, 1, guard);
+    const int rc = accflow_launch_gma_attn_stats(kp, qp, reinterpret_cast<float*>(ws), stats + (long long)b * 2 * P,
+                                                 1.0f / (fs * fs), P, D, Ppad, st);
+    if (rc) return rc;
+  }
+  ACCFLOW_RETURN_LAUNCH_STATUS();
+}
+
 extern "C" int accflow_conv_pack_f32(const float* w, const float* scale, int Cout, int Cin, int KH, int KW,
                                      int C0, int tap_major, float* wpack, int* ktab, void* stream) {
   if (!w || !wpack || !ktab || Cout <= 0 || Cin <= 0 || KH <= 0 || KW <= 0) return 1;

@@ -534,6 +534,19 @@ int accflow_launch_gma_attn(const void* kpack, const void* qpack, float* part, f
   ACCFLOW_RETURN_LAUNCH_STATUS();
 }
 
+// Pass 0 and the final statistics only (alternate_attention, gma_alt.hip: the probabilities are recomputed per iteration from
+// the packs and stats[P][2], nothing P x P is stored).
+int accflow_launch_gma_attn_stats(const void* kpack, const void* qpack, float* part, float* stats, float acc_scale, int P, int D,
+                                  int Ppad, hipStream_t st) {
+  gma_attn_args a;
+  a.kpack = kpack; a.qpack = qpack; a.part = part; a.stats = stats; a.out16 = nullptr;
+  a.acc_scale = acc_scale; a.P = P; a.D = D; a.Ppad = Ppad;
+  const int nb = cdiv(P, 128);
+  hipLaunchKernelGGL((gma_attn_gemm_kernel<0>), dim3(nb * nb), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(gma_attn_stats_kernel, dim3(cdiv(P, 256)), dim3(256), 0, st, part, stats, P, nb);
+  ACCFLOW_RETURN_LAUNCH_STATUS();
+}
+
 // LDS-ring form of corr_disp_gemm_kernel (fp16 split, two terms).  The register-only loop above lets every wave pull its
 // own A and B fragments from L2 - 8 KB per 12 MFMAs - and is bound by the vector memory pipe, not by the matrix cores or
 // the stores (profiles/r03_corr_gemm_store_ab.txt).  Here each operand byte enters the CU once per WORKGROUP: a 16-deep

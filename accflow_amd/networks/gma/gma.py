@@ -11,6 +11,9 @@ from .modules import Attention
 from .update import GMAUpdateBlock
 
 SHARE_ATTENTION = os.environ.get("ACCFLOW_GMA_SHARE_ATTENTION", "1") != "0"
+# alternate_attention for every GMA estimator (as if each one's args.alternate_attention were set): the aggregation from the
+# packs of q and k and the softmax statistics, no P x P attention matrix
+ALTERNATE_ATTENTION = os.environ.get("ACCFLOW_ALTERNATE_ATTENTION", "0") == "1"
 
 
 class RAFTGMA(RAFT):
@@ -25,6 +28,8 @@ class RAFTGMA(RAFT):
         args.corr_radius = 4
         if "dropout" not in self.args:
             self.args.dropout = 0
+        if "alternate_attention" not in self.args:
+            self.args.alternate_attention = False
         self.fnet = BasicEncoder(output_dim=256, norm_fn="instance", dropout=args.dropout)
         self.cnet = BasicEncoder(output_dim=hdim + cdim, norm_fn="batch", dropout=args.dropout)
         self.update_block = GMAUpdateBlock(self.args, hidden_dim=hdim)
@@ -32,6 +37,14 @@ class RAFTGMA(RAFT):
 
     def _x_dim(self):
         return 384
+
+    def _alternate_attention(self):
+        """alternate_attention, read at forward time (a build extension like AccFlow's warm_start: the reference has no such
+        flag): the aggregation recomputes the attention's probabilities in every iteration instead of reading a stored
+        matrix.  It runs in the default mode (fp16 split, S16 activations: ops.s16_active()); in fp32 mode, with
+        ACCFLOW_S16=0 and in the range guard's bf16x6 retry of a stage (ops.guard_report() names it) the stored matrix
+        runs as without the switch."""
+        return ALTERNATE_ATTENTION or bool(getattr(self.args, "alternate_attention", False))
 
     def _prepack(self):
         super()._prepack()
@@ -59,6 +72,9 @@ class RAFTGMA(RAFT):
                 else:
                     runs.append([slot[key], b, b + 1])
             inp = inp[reps].contiguous()
+        if self._alternate_attention() and ops.s16_active():
+            ws.attention = self.att.forward_alt(inp, runs=runs)
+            return
         ws.attention = self.att.forward_t(inp, runs=runs)
 
     def _iteration(self, ws, corr_fn, coords1, last):

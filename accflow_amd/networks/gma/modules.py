@@ -53,13 +53,28 @@ class Attention(nn.Module):
             return TransposedAttention(None, runs, attn16=ops.gma_attention_s16(qk, self.dim_head, self.scale))
         return TransposedAttention(ops.gma_attention_t(qk, self.dim_head, self.scale), runs)
 
+    @torch.no_grad()
+    def forward_alt(self, fmap, runs=None):
+        """alternate_attention: no matrix at all - the packs of q and k and the softmax statistics of every query
+        (ops.gma_attention_alt, 1 032 bytes per coarse pixel); Aggregate recomputes the probabilities in every refinement
+        iteration.  S16 mode only: in fp32 mode, with ACCFLOW_S16=0 and in a range-guard retry (bf16x6) the caller takes
+        forward_t / forward, the stored matrix."""
+        if self.heads != 1 or self.dim_head != 128 or self.args.position_only or self.args.position_and_content:
+            raise NotImplementedError("alternate_attention: only the single-head content attention with dim_head = 128")
+        if not ops.s16_active():
+            raise RuntimeError("alternate_attention runs in the fp16 split mode with S16 activations only")
+        require_cuda(fmap)
+        qk = ops.conv2d(self._packs.conv("qk", self.to_qk), fmap.float())
+        return TransposedAttention(None, runs, alt=ops.gma_attention_alt(qk, self.dim_head, self.scale))
+
 
 class TransposedAttention:
     """Hot-path handle: the attention stored j-major (see ops.gma_attention_t)."""
 
-    def __init__(self, attn_t, runs=None, attn16=None):
+    def __init__(self, attn_t, runs=None, attn16=None, alt=None):
         self.attn_t = attn_t
         self.attn16 = attn16   # ops.S16 (G, P, h, w): the pre-split form (then attn_t is None)
+        self.alt = alt         # ops.AltAttention: alternate_attention, no matrix stored (then attn_t and attn16 are None)
         self.runs = runs  # None: attn_t[b] belongs to item b; else [(g, b0, b1)]: items b0..b1-1 all use attn_t[g]
 
 
@@ -84,7 +99,7 @@ class Aggregate(nn.Module):
         fm = fmap.float().contiguous()
         require_cuda(fm)
         v = ops.conv2d(self._packs.conv("v", self.to_v), fm)
-        if isinstance(attn, TransposedAttention) and attn.attn16 is not None:
+        if isinstance(attn, TransposedAttention) and (attn.attn16 is not None or attn.alt is not None):
             if out is None:
                 out = torch.empty_like(fm)
             self._aggregate16(attn, v, fm, fm.stride(0), out, None)
@@ -114,6 +129,13 @@ class Aggregate(nn.Module):
         slices in place (fmap / out: (B, D, h, w) views with any batch stride, out16: ops.S16 or None)."""
         B, D, h, w = v.shape
         runs = attn.runs if attn.runs is not None else [(b, b, b + 1) for b in range(B)]
+        if attn.alt is not None:
+            for g, b0, b1 in runs:
+                ops.gma_aggregate_alt(attn.alt, g, v[b0:b1], fmap[b0].data_ptr(), fmap_bs,
+                                      self.gamma, out[b0].data_ptr() if out is not None else None, out.stride(0) if out is not None else 0,
+                                      out16.batch(b0, b1).ptr() if out16 is not None else None, out16.bs if out16 is not None else 0,
+                                      b1 - b0, D, h, w)
+            return
         a16 = attn.attn16
         item = a16.bs * 4
         for g, b0, b1 in runs:

@@ -1847,3 +1847,59 @@ def gma_aggregate_s16(attn16_item, v, fmap0, fmap_bs, gamma, out0, out_bs, out16
     _check(lib.accflow_gma_aggregate_s16(ctypes.c_void_p(attn16_item), _p(v), ctypes.c_void_p(fmap0), fmap_bs, _p(gamma),
                                          ctypes.c_void_p(out0), out_bs, ctypes.c_void_p(out16_0), out16_bs, _p(ws),
                                          _p(_guard(v.device)), n, D, H, W, _stream()), "accflow_gma_aggregate_s16")
+
+
+class AltAttention:
+    """What ops.gma_attention_alt keeps per distinct image1 instead of the P x P matrix: the fp16 hi / lo packs of k and q
+    (`packs`: uint8 (2, G, pack bytes), the k packs then the q packs) and the final softmax statistics (`stats`: float32 (G, P, 2) = {max_i,
+    1 / sum_i}).  `nbytes`: what the handle holds on the device."""
+    __slots__ = ("packs", "stats", "D", "H", "W")
+
+    def __init__(self, packs, stats, D, H, W):
+        self.packs, self.stats, self.D, self.H, self.W = packs, stats, D, H, W
+
+    @property
+    def nbytes(self):
+        return self.packs.numel() + self.stats.numel() * 4
+
+    def __len__(self):
+        return self.packs.shape[1]
+
+
+def gma_attention_alt(qk, D, scale):
+    """qk: (B, 2D, H, W) -> AltAttention: packs and row statistics of softmax_j(scale q_i . k_j), no matrix
+    (accflow_gma_attention_alt; D = 128 only)."""
+    lib = _lib.load()
+    qk = _dense(qk, "qk")
+    B, C2, H, W = qk.shape
+    if D != 128 or C2 != 2 * D:
+        raise RuntimeError("gma_attention_alt: D = 128 only (got D = %d, %d channels)" % (D, C2))
+    P = H * W
+    pack_bytes = 2 * (D // 8) * lib.accflow_conv_coutpad(P) * 16
+    packs = torch.empty((2, B, pack_bytes), dtype=torch.uint8, device=qk.device)
+    stats = torch.empty((B, P, 2), dtype=torch.float32, device=qk.device)
+    ws = torch.empty(lib.accflow_gma_attention_alt_ws_bytes(D, H, W), dtype=torch.uint8, device=qk.device)
+    _check(lib.accflow_gma_attention_alt(_p(qk), _p(packs[0]), _p(packs[1]), _p(stats), _p(ws), _p(_guard(qk.device)), B, D, H, W,
+                                         float(scale), _stream()), "accflow_gma_attention_alt")
+    return AltAttention(packs, stats, D, H, W)
+
+
+def gma_aggregate_alt(handle, g, v, fmap0, fmap_bs, gamma, out0, out_bs, out16_0, out16_bs, n, D, H, W):
+    """ops.gma_aggregate_s16 with attention g of an AltAttention handle in place of the stored matrix: fmap + gamma *
+    (attn @ v) for n items sharing it, the probabilities recomputed on the fly (accflow_gma_aggregate_alt)."""
+    lib = _lib.load()
+    if not isinstance(handle, AltAttention) or (handle.D, handle.H, handle.W) != (D, H, W) or not 0 <= g < len(handle):
+        raise RuntimeError("gma_aggregate_alt: the handle does not belong to these shapes")
+    v = _dense(v, "v")
+    if tuple(v.shape) != (n, D, H, W) or v.dtype != torch.float32:
+        raise RuntimeError("gma_aggregate_alt: v must be float32 (n, D, H, W)")
+    gamma = _dense(gamma.detach().float().contiguous(), "gamma")
+    nb = lib.accflow_gma_aggregate_alt_ws_bytes(n, D, H * W)
+    if nb <= 0:
+        raise RuntimeError("gma_aggregate_alt: D = 128 only")
+    ws = torch.empty(nb, dtype=torch.uint8, device=v.device)
+    _check(lib.accflow_gma_aggregate_alt(_p(handle.packs[0, g]), _p(handle.packs[1, g]),
+                                         _p(handle.stats[g]), _p(v), ctypes.c_void_p(fmap0), fmap_bs,
+                                         _p(gamma), ctypes.c_void_p(out0), out_bs, ctypes.c_void_p(out16_0), out16_bs, _p(ws),
+                                         _p(_guard(v.device)), n, D, H, W, _stream()), "accflow_gma_aggregate_alt")
+

@@ -567,6 +567,22 @@ long long accflow_gma_aggregate_s16_ws_bytes(int n, int D, int P);
 int accflow_gma_aggregate_s16(const void* attn16, const float* v, const float* fmap, long long fmap_bs, const float* gamma,
                               float* out, long long out_bs, void* out16, long long out16_bs, void* ws, int* guard, int n, int D,
                               int H, int W, void* stream);
+/* alternate_attention (csrc/gma_alt.hip): the same aggregation WITHOUT a stored attention matrix.  Once per image1,
+ * accflow_gma_attention_alt keeps what accflow_gma_attention_s16 builds on the way - the fp16 hi / lo packs of k and q
+ * (kpack, qpack: B packs of 2 * (D / 8) * accflow_conv_coutpad(H*W) * 16 bytes each) and the final softmax statistics
+ * stats (B, H*W, 2) = {max_i, 1 / sum_i} - and stops; ws: accflow_gma_attention_alt_ws_bytes(D, H, W) bytes, transient.
+ * Every iteration, accflow_gma_aggregate_alt recomputes the probabilities tile by tile from ONE item's packs and statistics
+ * and feeds them to the product with v * gamma from registers; the other arguments and the result are those of
+ * accflow_gma_aggregate_s16 (same operand arithmetic; the sums are taken in another order).  Deterministic: key splits meet
+ * in a fixed-order reduction, no float atomics.  D == 128 only (anything else returns 1); ws:
+ * accflow_gma_aggregate_alt_ws_bytes(n, D, P) bytes (0 for an unsupported D). */
+long long accflow_gma_attention_alt_ws_bytes(int D, int H, int W);
+int accflow_gma_attention_alt(const float* qk, void* kpack, void* qpack, float* stats, void* ws, int* guard, int B, int D, int H,
+                              int W, float scale, void* stream);
+long long accflow_gma_aggregate_alt_ws_bytes(int n, int D, int P);
+int accflow_gma_aggregate_alt(const void* kpack, const void* qpack, const float* stats, const float* v, const float* fmap,
+                              long long fmap_bs, const float* gamma, float* out, long long out_bs, void* out16, long long out16_bs,
+                              void* ws, int* guard, int n, int D, int H, int W, void* stream);
 int accflow_gma_attention_t_f32(const float* qk, float* attnT, void* ws, int mode, int B, int D, int H, int W,
                                 float scale, void* stream);
 long long accflow_gma_aggregate_ws_bytes(int B, int D, int P);
