@@ -88,6 +88,7 @@ SIGNATURES = {
     "accflow_conv2d_f32": [ctypes.POINTER(ConvDesc), c_f],
     "accflow_conv_stat_slots": [ctypes.POINTER(ConvDesc)],
     "accflow_conv_in_norm_supported": [ctypes.POINTER(ConvDesc)],
+    "accflow_conv_plan_query": [ctypes.POINTER(ConvDesc), ctypes.POINTER(c_i), c_i],
     "accflow_conv_gru16_supported": [],
     "accflow_instance_stats_finalize_f32": [c_f, c_i, c_f, c_i, c_i, ctypes.c_float, c_f],
     "accflow_instance_norm_apply_f32": [c_f, c_f, c_i, c_f, c_f, c_f, c_i, c_i, c_i, ctypes.c_float, c_i, c_f],

@@ -1016,6 +1016,30 @@ extern "C" int accflow_conv_stat_slots(const accflow_conv_desc* desc) {
   return !conv_validate(desc, d) && !conv_make_plan(d, true, p) ? p.slots : 0;
 }
 
+// The plan accflow_conv2d_f32 would launch this descriptor with, and whether it would accept it (0) or refuse it (1):
+// host only, launches nothing.  out[0..13]: family tc tp wc wp lay loop tapgemm norm w4 mode slots ch0 Z; with a tail split
+// (ch0 > 0) out[14], out[15]: the split-K parts of the head and of the tail, 0 otherwise.
+extern "C" int accflow_conv_plan_query(const accflow_conv_desc* desc, int* out, int n) {
+  if (!out || n < 16) return 1;
+  for (int i = 0; i < 16; ++i) out[i] = 0;
+  accflow_conv_desc d;
+  conv_plan p;
+  if (conv_validate(desc, d) || conv_make_plan(d, d.stats != nullptr, p)) return 1;
+  const int v[14] = {p.family, p.tc, p.tp, p.wc, p.wp, p.lay, p.loop, (int)p.tapgemm, (int)p.norm, (int)p.w4, p.mode, p.slots, p.ch0, p.Z};
+  for (int i = 0; i < 14; ++i) out[i] = v[i];
+  if (d.stats && p.slots != d.stat_slots) return 1;
+  if (d.in_norm && !p.can_norm) return 1;
+  if (p.ch0 > 0) {
+    accflow_conv_desc head, tail;
+    conv_plan ph, pt;
+    conv_tail_split(d, p.ch0, head, tail);
+    if (conv_plan_part(head, p, false, ph) || conv_plan_part(tail, p, true, pt)) return 1;
+    out[14] = ph.Z;
+    out[15] = pt.Z;
+  }
+  return 0;
+}
+
 extern "C" int accflow_conv2d_f32(const accflow_conv_desc* desc, void* stream) {
   accflow_conv_desc d;
   conv_plan p;

@@ -283,6 +283,11 @@ int accflow_conv2d_f32(const accflow_conv_desc* desc, void* stream);
 int accflow_conv_stat_slots(const accflow_conv_desc* desc);
 /* != 0 if the kernel chosen for this descriptor can apply accflow_conv_desc.in_norm */
 int accflow_conv_in_norm_supported(const accflow_conv_desc* desc);
+/* The plan accflow_conv2d_f32 would run this descriptor with, without launching anything (host only; tests pin the route of
+ * a call with it).  out[0..13] = family tc tp wc wp lay loop tapgemm norm w4 mode slots ch0 Z (csrc/conv_plan.h: conv_plan);
+ * when the launch is cut along the channels (ch0 > 0), out[14] / out[15] = the split-K parts of the head / of the tail, else 0.
+ * Returns 0 if accflow_conv2d_f32 would accept the descriptor, 1 if it would refuse it (or n < 16). */
+int accflow_conv_plan_query(const accflow_conv_desc* desc, int* out, int n);
 /* != 0 if the GRU epilogues can run on the pre-split state (accflow_conv_desc.e0_fmt / p32): the tap-specialised 5-tap
  * direct route is on (environment switches ACCFLOW_DIRECT_KT, ACCFLOW_DIRECT_W4 not 0, ACCFLOW_S16M 0 or unset; read
  * once per process).  Descriptors with e0_fmt or p32 set are refused (return 1) where this is 0. */

@@ -45,7 +45,7 @@ CONV_CASES = [
     # Cin, Cout, KH, KW, stride, padH, padW, B, H, W
     (3, 64, 7, 7, 2, 3, 3, 2, 40, 56),       # encoder stem
     (64, 64, 3, 3, 1, 1, 1, 2, 20, 28),
-    (64, 96, 3, 3, 2, 1, 1, 1, 20, 28),      # strided, 96-wide tile
+    (64, 96, 3, 3, 2, 1, 1, 1, 20, 28),      # strided, 96 channels (-> 64 ch x 64 px tiles at this size)
     (64, 96, 1, 1, 2, 0, 0, 1, 20, 28),      # downsample 1x1 s2
     (324, 256, 1, 1, 1, 0, 0, 1, 16, 32),    # convc1
     (256, 192, 3, 3, 1, 1, 1, 1, 16, 32),
@@ -73,8 +73,26 @@ CONV_CASES = [
 ]
 
 
+from test_conv_routes import trace  # noqa: E402,F401  (fixture: the plan of every accflow_conv2d_f32 call)
+
+# the CONV_CASES entries whose comments name a tile or a small-Cout kernel: (family, wc, wp, tc, tp) of the plan (conv_plan.h;
+# family 6 = fp32 MFMA, 1 = small-Cout patch kernel, 0 = small-Cout gather kernel)
+CONV_TILES = {
+    (64, 96, 3, 3, 2, 1, 1, 1, 20, 28): (6, 2, 2, 1, 1),
+    (128, 256, 3, 3, 1, 1, 1, 11, 60, 128): (6, 2, 2, 2, 2),
+    (128, 256, 3, 3, 1, 1, 1, 2, 60, 128): (6, 2, 2, 2, 1),
+    (128, 27, 3, 3, 1, 1, 1, 16, 60, 128): (6, 1, 4, 1, 2),
+    (64, 64, 3, 3, 1, 1, 1, 4, 120, 128): (6, 2, 2, 1, 2),
+    (64, 96, 3, 3, 2, 1, 1, 2, 240, 512): (6, 1, 4, 3, 1),
+    (96, 3, 1, 5, 1, 0, 2, 1, 9, 11): (1, 0, 0, 0, 0),
+    (8, 2, 3, 3, 1, 1, 1, 1, 10, 12): (0, 0, 0, 0, 0),
+    (40, 2, 3, 3, 2, 1, 1, 1, 10, 12): (0, 0, 0, 0, 0),
+}
+assert all(c in CONV_CASES for c in CONV_TILES)
+
+
 @pytest.mark.parametrize("case", CONV_CASES)
-def test_conv2d(ops, case):
+def test_conv2d(ops, case, trace):
     import torch.nn.functional as F
     Cin, Cout, KH, KW, st, pH, pW, B, H, W = case
     g = gen(hash(case) & 0xFFFF)
@@ -86,6 +104,10 @@ def test_conv2d(ops, case):
     out = ops.conv2d(pk, dev(x), mode=ops.CONV_F32)
     check(out, ref, 2e-5, what="conv %s" % (case,))
     check(ops.conv2d(pk, dev(x), act=ops.ACT_RELU, mode=ops.CONV_F32), torch.relu(ref), 2e-5, what="conv+relu")
+    assert len(trace) == 2 and all(rc == 0 for rc, _ in trace)
+    if case in CONV_TILES:
+        for _, p in trace:
+            assert (p["family"], p["wc"], p["wp"], p["tc"], p["tp"]) == CONV_TILES[case], (case, p)
 
 
 @pytest.mark.parametrize("mode,atol", [("bf16x3", 2e-3), ("bf16x6", 3e-5), ("f16x3", 1e-4)])

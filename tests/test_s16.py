@@ -25,6 +25,9 @@ def gen(seed):
     return torch.Generator().manual_seed(seed)
 
 
+from test_conv_routes import trace  # noqa: E402,F401  (fixture: the plan of every accflow_conv2d_f32 call)
+
+
 def test_to_s16_matches_the_split_and_round_trips(ops):
     g = gen(1)
     x = torch.randn(3, 21, 9, 13, generator=g) * torch.tensor([1e-3, 1.0, 50.0]).view(3, 1, 1, 1)
@@ -44,7 +47,7 @@ def test_to_s16_matches_the_split_and_round_trips(ops):
 CASES = [
     # Cin(s), Cout, KH, KW, B, H, W
     ((128,), 256, 3, 3, 2, 20, 40),
-    ((256,), 192, 3, 3, 1, 12, 64),        # 128 + 64 channel cut of the launch
+    ((256,), 192, 3, 3, 1, 12, 64),        # split-K, Z = 4 (the 128 + 64 channel cut: test_conv_s16_tail_cut_without_a_workspace)
     ((128,), 64, 3, 3, 2, 13, 37),         # 64-channel kernel, ragged tiles
     # (1x1 convolutions of < 512 channels on small grids go to the im2col kernel in the fp32-activation path - another
     # summation order - so the bit comparison needs grids of >= 300 workgroups, where both paths run the direct kernel)
@@ -96,6 +99,49 @@ def test_conv_s16_in_and_out_bit_identical(ops, case):
         o16b.data.fill_(0x7B7B7B7B)
         r = ops.conv2d(pk, x16[0], x16[1] if len(xs) > 1 else None, act=act, out16=o16b, fp32_out=False)
         assert r is o16b and torch.equal(o16b.data, o16.data)
+    assert not ops.guard_tripped()
+
+
+def test_conv_s16_tail_cut_without_a_workspace(ops, trace):
+    """CASES[1] under ops.ksplit_scope(False): with no split-K workspace on offer the 192-channel launch is cut into 128
+    channels on the 128-channel kernel and 64 on the 64-channel one (plan.ch0 == 128, asserted from the trace of every call).
+    The S16 forms stay bit-identical among themselves - fp32 or S16 sources, fp32 and / or S16 destination: the same cut, the
+    same summation order.  The plain fp32-activation twin cannot be part of that here: without a workspace its 12 workgroups
+    are diverted to the im2col kernel (another summation order; asserted), so the results are compared with float64 at the
+    f16x3 gate of tests/test_hip_parity.py::test_conv2d_split_bf16 (1e-4) instead."""
+    import torch.nn.functional as F
+    from test_conv_routes import DIRECT, IM2COL
+    cins, Cout, KH, KW, B, H, W = CASES[1]
+    g = gen(7)
+    x = torch.randn(B, cins[0], H, W, generator=g)
+    w = torch.randn(Cout, cins[0], KH, KW, generator=g) * (1.0 / (cins[0] * KH * KW)) ** 0.5
+    b = torch.randn(Cout, generator=g) * 0.1
+    pk = ops.PackedConv(dev(w), dev(b), padding=(KH // 2, KW // 2))
+    x32 = dev(x)
+    x16 = ops.to_s16(x32)
+    with ops.ksplit_scope(False):
+        for act in (ops.ACT_NONE, ops.ACT_RELU):
+            del trace[:]
+            ref = F.conv2d(x.double(), w.double(), b.double(), padding=(KH // 2, KW // 2))
+            if act == ops.ACT_RELU:
+                ref = torch.relu(ref)
+            twin = ops.conv2d(pk, x32, act=act)
+            assert trace[-1][0] == 0 and trace[-1][1]["family"] == IM2COL, trace[-1]
+            assert float((twin.cpu().double() - ref).abs().max()) <= 1e-4
+            got = ops.conv2d(pk, x16, act=act)                              # S16 in, fp32 out
+            o16 = ops.S16.empty(B, Cout, H, W, got.device)
+            o16.data.fill_(0x7B7B7B7B)
+            got2 = ops.conv2d(pk, x32, act=act, out16=o16)                  # fp32 in, fp32 + S16 out
+            o16b = ops.S16.empty(B, Cout, H, W, got.device)
+            o16b.data.fill_(0x7B7B7B7B)
+            r = ops.conv2d(pk, x16, act=act, out16=o16b, fp32_out=False)    # S16 in, S16 out only
+            for rc, p in trace[1:]:
+                assert rc == 0 and p["family"] == DIRECT and p["ch0"] == 128 and p["Z"] == 1 and (p["Zhead"], p["Ztail"]) == (1, 1), p
+            assert len(trace) == 4
+            assert float((got.cpu().double() - ref).abs().max()) <= 1e-4
+            assert torch.equal(got, got2), "S16 input changes the result"
+            assert torch.equal(o16.data, ops.to_s16(got2).data), "the S16 copy is the split of the fp32 result"
+            assert r is o16b and torch.equal(o16b.data, o16.data)
     assert not ops.guard_tripped()
 
 
