@@ -215,9 +215,9 @@ def convex_upsample(flow, mask):
 # R10  RAFT.forward (raft/raft.py:94-146) and R11/R12 GMA (gma/gma.py:70-125, gma/modules.py)
 
 
-def coords_grid(B, H, W):
+def coords_grid(B, H, W, dtype=torch.float32):
     ys, xs = torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij")
-    return torch.stack([xs, ys], 0).float()[None].repeat(B, 1, 1, 1)
+    return torch.stack([xs, ys], 0).to(dtype)[None].repeat(B, 1, 1, 1)
 
 
 def gma_attention(inp, sd, p="att"):
@@ -251,7 +251,7 @@ def raft_forward(sd, image1, image2, iters=12, flow_init=None, gma=False, return
     net, inp = torch.tanh(cnet[:, :128]), torch.relu(cnet[:, 128:])
     attention = gma_attention(inp, sd) if gma else None
     H8, W8 = fmap1.shape[2:]
-    coords0 = coords_grid(B, H8, W8)
+    coords0 = coords_grid(B, H8, W8, dtype=fmap1.dtype)     # (the oracle runs in the dtype of its inputs: float64 in tests)
     coords1 = coords0.clone()
     if flow_init is not None:
         coords1 = coords1 + flow_init
@@ -304,8 +304,8 @@ def downflow8(flow):
     N, C, H, W = flow.shape
     assert H % 8 == 0 and W % 8 == 0
     h, w = H // 8, W // 8
-    sy = torch.arange(h, dtype=torch.float32) * (float(H - 1) / float(h - 1) if h > 1 else 0.0)
-    sx = torch.arange(w, dtype=torch.float32) * (float(W - 1) / float(w - 1) if w > 1 else 0.0)
+    sy = torch.arange(h, dtype=flow.dtype) * (float(H - 1) / float(h - 1) if h > 1 else 0.0)
+    sx = torch.arange(w, dtype=flow.dtype) * (float(W - 1) / float(w - 1) if w > 1 else 0.0)
     y0, x0 = sy.long(), sx.long()
     y1 = torch.where(y0 < H - 1, y0 + 1, y0)
     x1 = torch.where(x0 < W - 1, x0 + 1, x0)
