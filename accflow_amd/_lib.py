@@ -164,6 +164,14 @@ SIGNATURES = {
                                          c_i, c_f],
 }
 
+# the size queries: element / byte / word counts that may pass 2^31 come back as long long, everything else as int
+RETURNS_LONGLONG = frozenset((
+    "accflow_conv_patch_elems", "accflow_conv_multi_pack_elems", "accflow_corr_pack_bytes", "accflow_corr_volume_ws_bytes",
+    "accflow_gma_aggregate_ws_bytes", "accflow_gma_attention_ws_bytes", "accflow_gma_aggregate_s16_ws_bytes",
+    "accflow_gma_attention_s16_ws_bytes", "accflow_gma_attention_alt_ws_bytes", "accflow_gma_aggregate_alt_ws_bytes",
+    "accflow_corr_disp_level_elems", "accflow_corr_alt_pyramid_elems", "accflow_s16_item_words",
+))
+
 _lock = threading.Lock()
 _lib = None
 
@@ -196,9 +204,7 @@ def load():
         for name, argtypes in SIGNATURES.items():
             fn = getattr(lib, name)  # AttributeError if a declared symbol is missing
             fn.argtypes = argtypes
-            fn.restype = ctypes.c_longlong if name in ("accflow_conv_patch_elems", "accflow_conv_multi_pack_elems", "accflow_corr_pack_bytes", "accflow_corr_volume_ws_bytes",
-                                                    "accflow_gma_aggregate_ws_bytes", "accflow_gma_attention_ws_bytes", "accflow_gma_aggregate_s16_ws_bytes", "accflow_gma_attention_s16_ws_bytes", "accflow_gma_attention_alt_ws_bytes", "accflow_gma_aggregate_alt_ws_bytes", "accflow_corr_disp_level_elems", "accflow_corr_alt_pyramid_elems",
-                                                    "accflow_s16_item_words") else ctypes.c_int
+            fn.restype = ctypes.c_longlong if name in RETURNS_LONGLONG else ctypes.c_int
         if lib.accflow_abi_version() != ABI_VERSION:
             raise RuntimeError("accflow_amd: ABI version mismatch")
         if (lib.accflow_conv_desc_bytes() != ctypes.sizeof(ConvDesc) or lib.accflow_conv_src_bytes() != ctypes.sizeof(ConvSrc)):

@@ -288,7 +288,7 @@ class BasicUpdateBlock(nn.Module):
         pk, f = self._packs, self.flow_head
         if ws.s16:
             D = ws.descs
-            if coords1 is not None and ops.profiler.ACTIVE is None and "fh12" in D and D["fh12"][1] is coords1:   # replay both launches
+            if coords1 is not None and ops.profiler.ACTIVE is None and "fh12" in D and D["fh12"][2] is coords1:   # replay both launches
                 return ops.conv2d_tapgemm(None, None, None, cache=(D, "fh12"))
             p1, p2 = pk.conv("fh1", f.conv1), pk.conv("fh2", f.conv2)
             if ops.tapgemm_eligible(p1, p2, ws.h16):

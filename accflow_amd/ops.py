@@ -5,6 +5,7 @@ and streams; no torch operator computes anything here.
 Every function raises RuntimeError when a tensor is not a float32 CUDA tensor or when the kernel
 library reports an error - there is no CPU / eager fallback.
 """
+import collections
 import contextlib
 import ctypes
 import functools
@@ -477,6 +478,232 @@ USE_NORM_STATS = os.environ.get("ACCFLOW_NORM_STATS", "1") == "1"
 USE_NORM_ON_LOAD = os.environ.get("ACCFLOW_NORM_ON_LOAD", "1") == "1"
 
 
+def _replay(cache, name):
+    """Re-issue a launch whose argument list a previous call with the same `cache` = (dict, key) stored (same tensors: the
+    refinement iterations); None when there is nothing to replay."""
+    if cache is None or profiler.ACTIVE is not None:
+        return None
+    hit = cache[0].get(cache[1])
+    if hit is None:
+        return None
+    _check(hit[0](*hit[1], _stream()), name + " (cached)")
+    return hit[2]
+
+
+def _launch(fn, args, name, timer=None, cache=None, ret=None, keep=None):
+    """The launch tail of every op that is timed or replayed: fn(*args, stream), checked; returns `ret`.
+    timer = (op name, figures): when the per-launch profiler wants that op the launch is bracketed and figures() ->
+    (work[, detail[, work_exec]]) is evaluated - only then.  cache = (dict, key): unless a profiler is active (the predicate
+    _replay() re-issues under) the entry (fn, args, ret, keep) is stored; `keep` holds every tensor `args` points at."""
+    tm = profiler.ACTIVE
+    if tm is not None and timer is not None and tm.wants(timer[0]):
+        t0 = tm.begin()
+        _check(fn(*args, _stream()), name)
+        tm.end(timer[0], t0, *timer[1]())
+        return ret
+    _check(fn(*args, _stream()), name)
+    if cache is not None and tm is None:
+        cache[0][cache[1]] = (fn, args, ret, keep)
+    return ret
+
+
+# The four forms of a convolution call.  _conv_desc() fills the descriptor of all of them; every way they differ is a column
+# here, or the `kws_ok` / `stats` argument at the call.  The differences are behaviour and kept as they were found (DESIGN.md,
+# "Known asymmetries of the convolution forms"); where one looks accidental the column says so.
+#   who          the entry point named in error texts
+#   s16_src      sources may be ops.S16 (in_fmt); the fp32 form hands them to _plane4, which refuses them
+#   via_multi    S16_VIA_MULTI mirrors S16 sources into d.src[] (A/B switch of the in0 / in1 S16 form only)
+#   patch_switch USE_PATCH = False withholds wpatch, and wpatch16 with it (looks accidental: the S16 forms ignore the switch)
+#   f16_always   fp16 packs + range guard whatever the mode; False: in f16x3 mode only, and only when the pack has wscale16
+#   wsplit       the im2col packs wsplit / wsplit16 travel when the pack has them (tapgemm leaves them out)
+#   alloc_out    when `out` is None it is allocated: "always" / "fp32" = fp32_out or GRU_ZR / "fp32_or_lone" = that, or no out16
+#                either / "never" (tapgemm: the descriptor has no fp32 destination, `out` belongs to the tap sum)
+#   s16_e0       an ops.S16 `e0`: None = refused (_plane4) / "gru" = the GRU epilogues' state, shape (B, n_out, OH, OW), sets p32 /
+#                "any" = any epilogue, shape (B, Cout, OH, OW), no p32, the split-K offer taken back (Cout against n_out looks
+#                accidental: the two agree except under GRU_ZR)
+_Form = collections.namedtuple("_Form", "who s16_src via_multi patch_switch f16_always wsplit alloc_out s16_e0")
+_FORM_F32 = _Form("conv2d", s16_src=False, via_multi=False, patch_switch=True, f16_always=False, wsplit=True,
+                  alloc_out="always", s16_e0=None)
+_FORM_S16 = _Form("conv2d", s16_src=True, via_multi=True, patch_switch=False, f16_always=True, wsplit=True,
+                  alloc_out="fp32", s16_e0="gru")
+_FORM_TAPGEMM = _Form("conv2d_tapgemm", s16_src=True, via_multi=False, patch_switch=False, f16_always=True, wsplit=False,
+                      alloc_out="never", s16_e0=None)
+_FORM_MULTI = _Form("conv2d_multi", s16_src=True, via_multi=False, patch_switch=False, f16_always=True, wsplit=False,
+                    alloc_out="fp32_or_lone", s16_e0="any")
+
+
+def _set_src(s, ptr, bs, C, Hs, Ws, geo):
+    s.ptr, s.bs, s.C, s.Hs, s.Ws = ptr, bs, C, Hs, Ws
+    s.step, s.oy, s.ox, s.KH, s.KW, s.padH, s.padW = geo
+
+
+def _conv_desc(form, pk, srcs, act, epi, md, out=None, out16=None, fp32_out=True, e0=None, e1=None, out2=None, pre=None,
+               p32_out=False, offset=None, dmask=None, in_norm=None, stats=False, kws_ok=False, out_hw=None, lay=None, tg=None):
+    """The accflow_conv_desc of one launch -> (d, ret, ConvStats or None, keep), or None when `in_norm` is given and the
+    kernel planned for the descriptor cannot normalise on load.  ret: what the op returns (the fp32 destination, or out16 when
+    that is the only one asked for); keep: every tensor the descriptor points at.
+    srcs: (in0, in1) for a PackedConv, the source list for a PackedMulti (then out_hw = the output size, lay = a forced wave
+    layout).  kws_ok: the form's own condition for offering a split-K workspace; stats: ask for InstanceNorm statistics slots;
+    tg = (tap pack, tap-row tensor) of ACCFLOW_EPI_TAPGEMM."""
+    lib = _lib.load()
+    who = form.who
+    d = ConvDesc()
+    # ---- sources, geometry, weight packs
+    if form is _FORM_MULTI:
+        # the kernel reads each source's geometry from d.src[]: H, W are the OUTPUT size, the shape a 1x1 stride-1 one, and
+        # there is no wpack / ktab / Kpad
+        B = srcs[0].shape[0]
+        OH, OW = out_hw
+        d.nsrc = len(srcs)
+        for k, (t, c, g) in enumerate(zip(srcs, pk.C, pk.geo)):
+            if not isinstance(t, S16) or t.C != c or t.shape[0] != B:
+                raise RuntimeError("conv2d_multi: source %d must be an ops.S16 of %d channels and batch %d" % (k, c, B))
+            _set_src(d.src[k], t.ptr(), t.bs, c, t.shape[2], t.shape[3], g)
+        if lay is not None:
+            d.src[0].reserved = int(lay) + 1      # tests / tuning: force a wave layout
+        d.H, d.W = OH, OW
+        d.KH = d.KW = d.stride = 1
+        d.split_c0 = pk.split_c0
+        d.wpatch16, d.wscale16 = pk.wpatch16.data_ptr(), pk.wscale16.data_ptr()
+    else:
+        in0, in1 = srcs
+        fmt, S = 0, []     # S[k] = (pointer, batch stride, channels)
+        for k, t in enumerate(srcs):
+            if t is None:
+                S.append((None, 0, 0))
+            elif form.s16_src and isinstance(t, S16):
+                fmt |= 1 << k
+                S.append((t.ptr(), t.bs, t.C))
+            else:
+                bs = _plane4(t, "in%d" % k)
+                S.append((t.data_ptr(), bs, t.shape[1]))
+        if fmt and fmt != (3 if in1 is not None else 1):
+            raise RuntimeError("%s: both sources must have the same format" % who)
+        B, _, H, W = in0.shape
+        if in1 is not None and (in1.shape[0] != B or tuple(in1.shape[2:]) != (H, W)):
+            raise RuntimeError("%s: in0/in1 shape mismatch" % who)
+        C0, C1 = S[0][2], S[1][2]
+        if C0 != pk.C0 or C0 + C1 != pk.Cin:
+            raise RuntimeError("%s: channel split (%d,%d) does not match packed weights (C0=%d, Cin=%d)"
+                               % (who, C0, C1, pk.C0, pk.Cin))
+        OH, OW = pk.out_size(H, W)
+        (d.in0, d.in0_bs, _), (d.in1, d.in1_bs, _) = S
+        d.in_fmt = fmt
+        if form.via_multi and S16_VIA_MULTI and fmt:
+            # the same convolution through the multi-source kernel (same pack, same results; per-call switch for A/B runs)
+            d.nsrc = 2 if in1 is not None else 1
+            for k in range(d.nsrc):
+                _set_src(d.src[k], S[k][0], S[k][1], S[k][2], H, W, (1, 0, 0, pk.KH, pk.KW, pk.padH, pk.padW))
+        d.C0, d.C1, d.H, d.W = C0, C1, H, W
+        d.KH, d.KW, d.stride, d.padH, d.padW = pk.KH, pk.KW, pk.stride, pk.padH, pk.padW
+        d.wpack, d.ktab, d.Kpad = pk.wpack.data_ptr(), pk.ktab.data_ptr(), pk.Kpad
+        if form.wsplit and pk.wsplit is not None:
+            d.wsplit = pk.wsplit.data_ptr()
+        if pk.wpatch is not None and (USE_PATCH or not form.patch_switch):
+            d.wpatch = pk.wpatch.data_ptr()
+        if form.f16_always or (md == CONV_F16X3 and pk.wscale16 is not None):
+            if d.wpatch and pk.wpatch16 is not None:
+                d.wpatch16 = pk.wpatch16.data_ptr()
+            if form.wsplit and pk.wsplit16 is not None:   # (the stem kernel - 7x7 stride 2 of the image - reads the im2col fp16 pack)
+                d.wsplit16 = pk.wsplit16.data_ptr()
+            d.wscale16 = pk.wscale16.data_ptr()
+    dev = srcs[0].device
+    if d.wscale16:
+        d.guard = _guard(dev).data_ptr()
+    d.B, d.OH, d.OW, d.Cout, d.CoutPad = B, OH, OW, pk.Cout, pk.CoutPad
+    d.bias = pk.bias.data_ptr() if pk.bias is not None else None
+    d.act, d.epi, d.mode = act, epi, md
+    # ---- destinations
+    n_out = pk.Cout // 2 if epi == EPI_GRU_ZR else pk.Cout
+    if out is None and form.alloc_out != "never" and (form.alloc_out == "always" or fp32_out or epi == EPI_GRU_ZR
+                                                      or (form.alloc_out == "fp32_or_lone" and out16 is None)):
+        out = torch.empty((B, n_out, OH, OW), dtype=torch.float32, device=dev)
+    if out is not None:
+        d.out_bs = _plane4(out, "out")
+        if tuple(out.shape) != (B, n_out, OH, OW):
+            raise RuntimeError("%s: out shape %s != %s" % (who, tuple(out.shape), (B, n_out, OH, OW)))
+        d.out = out.data_ptr()
+    if out16 is not None:
+        if tuple(out16.shape) != (B, n_out, OH, OW):
+            raise RuntimeError("%s: out16 shape %s != %s" % (who, out16.shape, (B, n_out, OH, OW)))
+        d.out16, d.out16_bs = out16.ptr(), out16.bs
+    # ---- the split-K workspace offer (the C side decides whether to split): small grids - the batch-1 fusion chain - get
+    # scratch for 4 K-parts, summed by a second kernel
+    ws = None
+    if kws_ok and _ksplit_on() and B * OH * OW <= KSPLIT_MAX_PIXELS and pk.Cout > 4:
+        ws = _ksplit_ws(4 * B * pk.Cout * OH * OW, dev)
+        d.kws, d.kws_elems = ws.data_ptr(), ws.numel()
+    # ---- epilogue operands
+    if form.s16_e0 == "gru" and isinstance(e0, S16):
+        # the GRU state kept pre-split only (accflow_conv_desc.e0_fmt, GRU_ZR / GRU_Q of the 5-tap convolutions): the epilogue
+        # reads h = (hi + lo) / 2^4 with 8-byte block loads
+        if epi not in (EPI_GRU_ZR, EPI_GRU_Q) or tuple(e0.shape) != (B, n_out, OH, OW):
+            raise RuntimeError("conv2d: an S16 e0 is the GRU epilogues' state operand, shape (B, hidden, OH, OW)")
+        d.e0_bs, d.e0, d.e0_fmt = e0.bs, e0.ptr(), 1
+        d.p32 = 3 if epi == EPI_GRU_ZR else 6      # z out + pre / pre + e1 (z) in the pixel-major layout
+    elif form.s16_e0 == "any" and isinstance(e0, S16):     # residual operand kept pre-split only (the encoders' block input)
+        if tuple(e0.shape) != (B, pk.Cout, OH, OW):
+            raise RuntimeError("conv2d_multi: S16 e0 shape %s != %s" % (e0.shape, (B, pk.Cout, OH, OW)))
+        d.e0_bs, d.e0, d.e0_fmt = e0.bs, e0.ptr(), 1
+        d.kws, d.kws_elems = None, 0               # (taken back after the offer: the scratch buffer has grown all the same)
+    elif e0 is not None:
+        d.e0_bs, d.e0 = _plane4(e0, "e0"), e0.data_ptr()
+    if e1 is not None:
+        d.e1_bs, d.e1 = _plane4(e1, "e1"), e1.data_ptr()
+    if out2 is not None:
+        d.out2_bs, d.out2 = _plane4(out2, "out2"), out2.data_ptr()
+    if pre is not None:  # pre-activation addend of the GRU epilogues, (B, Cout, OH, OW)
+        if epi not in (EPI_GRU_ZR, EPI_GRU_Q) or tuple(pre.shape) != (B, pk.Cout, OH, OW):
+            raise RuntimeError("%s: `pre` is a (B, Cout, OH, OW) addend of the GRU epilogues" % who)
+        d.pre_bs, d.pre = _plane4(pre, "pre"), pre.data_ptr()
+    if p32_out:
+        if epi != EPI_STORE or out is None or pk.Cout % 128 or isinstance(e0, S16):
+            raise RuntimeError("conv2d: p32_out is a plain fp32 store onto a multiple of 128 channels")
+        d.p32 = 1
+    if offset is not None:
+        d.offset_bs, d.offset = _plane4(offset, "offset"), offset.data_ptr()
+        d.dmask_bs, d.dmask = _plane4(dmask, "dmask"), dmask.data_ptr()
+        if not pk.tap_major:
+            raise RuntimeError("deformable conv needs tap-major packed weights")
+    if tg is not None:
+        pz, z = tg
+        rows = pz.Cout
+        d.tg_w16, d.tg_scale, d.tg_out = pz.wpatch16.data_ptr(), pz.wscale16.data_ptr(), z.data_ptr()
+        d.tg_out_bs, d.tg_out_ps, d.tg_rows, d.tg_coutpad = rows * OH * OW, B * rows * OH * OW, rows, pz.CoutPad
+    # ---- the two questions to the plan, in this order: normalise-on-load is asked BEFORE d.in_norm is set, the statistics
+    # slots on the descriptor as it then stands
+    if in_norm is not None:
+        # in0 = the raw output of a convolution; in_norm = its (B, C0, 2) {mean, rstd} (instance_stats_finalize): the
+        # kernel reads relu((x - mean) * rstd).  None is returned if the kernel chosen for this call cannot do that.
+        if srcs[1] is not None or tuple(_dense(in_norm, "in_norm").shape) != (B, d.C0, 2):
+            raise RuntimeError("conv2d: in_norm is (B, C0, 2) for a single-source input")
+        if not lib.accflow_conv_in_norm_supported(ctypes.byref(d)):
+            return None
+        d.in_norm = in_norm.data_ptr()
+    st = None
+    if stats:
+        slots = lib.accflow_conv_stat_slots(ctypes.byref(d))
+        if slots > 0:
+            st = ConvStats(torch.empty((B, pk.Cout, slots, 3), dtype=torch.float32, device=dev), slots)
+            d.stats, d.stat_slots = st.partial.data_ptr(), slots
+    ret = out if (out is not None and (fp32_out or out16 is None)) else out16
+    # (the split-K scratch d.kws points into is kept too: _ksplit_ws drops its buffer when a later conv asks for a larger one)
+    return d, ret, st, (d, pk, srcs, out, out16, e0, e1, out2, pre, ws, offset, dmask, in_norm, tg)
+
+
+def _conv_figures(pk, d, tag, algo_cin):
+    """The profiler's (algorithmic flop, detail, executed flop) of a PackedConv launch.  algo_cin: input channels of the
+    convolution this launch stands for in the reference's formulation: the GRU gate convs run over 2/3 of their input channels
+    per iteration, the context third being convolved once per pair (algo_cin = 0 there) - the algorithmic work is the
+    reference's full conv per iteration."""
+    B, OH, OW = d.B, d.OH, d.OW
+    acin = pk.Cin if algo_cin is None else algo_cin
+    return (2.0 * acin * pk.KH * pk.KW * pk.Cout * B * OH * OW,
+            "Cin%d Cout%d k%dx%d s%d B%d %dx%d%s%s" % (pk.Cin, pk.Cout, pk.KH, pk.KW, pk.stride, B, OH, OW, tag,
+                                                      "" if algo_cin is None else " (stands for Cin%d)" % algo_cin),
+            2.0 * pk.Cin * pk.KH * pk.KW * pk.Cout * B * OH * OW)
+
+
 def conv2d(pk, in0, in1=None, out=None, act=ACT_NONE, epi=EPI_STORE, e0=None, e1=None, out2=None,
            offset=None, dmask=None, mode=None, want_stats=False, pre=None, algo_cin=None, in_norm=None, out16=None,
            fp32_out=True, cache=None, p32_out=False):
@@ -490,21 +717,20 @@ def conv2d(pk, in0, in1=None, out=None, act=ACT_NONE, epi=EPI_STORE, e0=None, e1
     (accflow_conv_desc.p32; ops.from_p32 gives NCHW back) - what the GRU epilogues read their context addend in.  With an
     ops.S16 `e0` (GRU_ZR / GRU_Q, 1x5 / 5x1): the packed-operand GRU epilogue - `pre`, `e1` (z) and GRU_ZR's `out` (z) are
     pixel-major tensors, the state is read from / written to S16 tensors only.
+    algo_cin: profiler accounting only, see _conv_figures.
     cache = (dict, key): a call site that repeats with the SAME tensors (the 12 refinement iterations run the same
     convolutions on the same workspace buffers) keeps its filled descriptor there and re-launches it without rebuilding
     it - most of the host time of a launch; only S16 calls use it, and not while the per-launch profiler is active."""
-    if cache is not None and profiler.ACTIVE is None:
-        hit = cache[0].get(cache[1])
-        if hit is not None:
-            _check(_lib.load().accflow_conv2d_f32(ctypes.byref(hit[0]), _stream()), "accflow_conv2d_f32 (cached)")
-            return hit[1]
+    r = _replay(cache, "accflow_conv2d_f32")
+    if r is not None:
+        return r
     if pk is None:
         # a replay call site (pk / tensors omitted) without a stored descriptor: the per-launch profiler was switched on
         # between two iterations of one refinement, or the cache was cleared - the caller must pass the real arguments
         raise RuntimeError("conv2d: no packed weights given and no cached descriptor for %r to replay"
                            % (cache[1] if cache is not None else None,))
-    if isinstance(in0, S16) and pk.Cout <= 4 and out16 is None and (
-            pk.ztaps is None or ((current_mode() if mode is None else mode) == CONV_F16X3 and not TAPSUM_F16)):
+    md = current_mode() if mode is None else mode
+    if isinstance(in0, S16) and pk.Cout <= 4 and out16 is None and (pk.ztaps is None or (md == CONV_F16X3 and not TAPSUM_F16)):
         # a <= 4-channel regression fed a pre-split tensor while the tap-sum path is switched off (ACCFLOW_CONV_TAPSUM=0) or
         # held on bf16x6 (ACCFLOW_TAPSUM_F16=0; both A/B switches): the kernels that then run read fp32, and (hi + lo) / 2^4
         # is the tensor's value to 22 bits
@@ -513,27 +739,28 @@ def conv2d(pk, in0, in1=None, out=None, act=ACT_NONE, epi=EPI_STORE, e0=None, e1
     if (out16 is not None or isinstance(in0, S16)) and not (pk.ztaps is not None and out16 is None):
         if want_stats or offset is not None or in_norm is not None:
             raise RuntimeError("conv2d: S16 tensors are for plain direct-kernel convolutions")
-        return _conv2d_s16(pk, in0, in1, out, act, epi, e0, e1, out2, mode, pre, algo_cin, out16, fp32_out, cache, p32_out)
+        if md != CONV_F16X3 or (pk.wpatch16 is None and pk.wsplit16 is None):
+            raise RuntimeError("conv2d: S16 tensors need the f16x3 mode and a direct-kernel weight pack")
+        # split-K: not with the packed-operand GRU epilogue, not onto a pixel-major destination
+        d, ret, _, keep = _conv_desc(_FORM_S16, pk, (in0, in1), act, epi, md, out, out16, fp32_out, e0, e1, out2, pre, p32_out,
+                                     kws_ok=not isinstance(e0, S16) and not p32_out)
+        return _launch(_lib.load().accflow_conv2d_f32, (ctypes.byref(d),), "accflow_conv2d_f32 (S16)",
+                       ("conv2d", lambda: _conv_figures(pk, d, " S16in" if d.in_fmt else " S16", algo_cin)), cache, ret, keep)
     if p32_out or isinstance(e0, S16):
         raise RuntimeError("conv2d: pixel-major / pre-split operands belong to the S16 direct-kernel form")
     if want_stats:
         if act != ACT_NONE or epi != EPI_STORE or offset is not None:
             raise RuntimeError("conv2d: statistics are gathered for plain convolutions only (store, no activation)")
-        holder = []
-        o = _conv2d(pk, in0, in1, out, act, epi, e0, e1, out2, offset, dmask, mode, holder, None, None, in_norm)
-        if o is None:
-            return None   # (in_norm given but the kernel chosen for this call cannot normalise on load)
-        return o, (holder[0] if holder else None)
-    return _conv2d(pk, in0, in1, out, act, epi, e0, e1, out2, offset, dmask, mode, None, pre, algo_cin, in_norm)
+        pre = algo_cin = None      # (as ever: a statistics call drops both)
+    r = _conv2d(pk, in0, in1, out, act, epi, e0, e1, out2, offset, dmask, md, want_stats, pre, algo_cin, in_norm)
+    if r is None:
+        return None   # (in_norm given but the kernel chosen for this call cannot normalise on load)
+    return r if want_stats else r[0]
 
 
-def _conv2d(pk, in0, in1, out, act, epi, e0, e1, out2, offset, dmask, mode, stats_holder, pre=None, algo_cin=None,
-            in_norm=None):
-    """algo_cin: input channels of the convolution this launch stands for in the reference's formulation (profiler
-    accounting only): the GRU gate convs run over 2/3 of their input channels per iteration, the context third being
-    convolved once per pair (algo_cin = 0 there) - the algorithmic work is the reference's full conv per iteration."""
+def _conv2d(pk, in0, in1, out, act, epi, e0, e1, out2, offset, dmask, md, want_stats, pre, algo_cin, in_norm):
+    """The fp32-tensor form -> (out, ConvStats or None), or None (_conv_desc): two diversions, then the plain launch."""
     lib = _lib.load()
-    md = current_mode() if mode is None else mode
     if (pk.ztaps is not None and md != CONV_F32 and offset is None and epi in (EPI_STORE, EPI_ACCUM, EPI_RES_RELU)
             and (isinstance(in0, S16) or in0.shape[0] * in0.shape[2] * in0.shape[3] >= TAPSUM_MIN_PIXELS)):
         z = conv2d(pk.ztaps, in0, in1, mode=CONV_BF16X6 if (md == CONV_F16X3 and not TAPSUM_F16) else md)
@@ -542,215 +769,35 @@ def _conv2d(pk, in0, in1, out, act, epi, e0, e1, out2, offset, dmask, mode, stat
             out = torch.empty((B, pk.Cout, H, W), dtype=torch.float32, device=in0.device)
         out_bs = _plane4(out, "out")
         e0_bs = _plane4(e0, "e0") if e0 is not None else 0
-        tm = profiler.ACTIVE
-        t0 = tm.begin() if tm is not None and tm.wants("conv2d") else None
-        _check(lib.accflow_tap_sum_f32(_p(z), _p(pk.bias) if pk.bias is not None else None, _p(e0) if e0 is not None else None,
-                                       e0_bs, _p(out), out_bs, B, pk.Cout, H, W, pk.KH, pk.KW, pk.padH, pk.padW, int(act),
-                                       int(epi), _stream()), "accflow_tap_sum_f32")
-        if t0 is not None:
-            tm.end("conv2d", t0, 0.0, "tap_sum Cout%d k%dx%d B%d %dx%d" % (pk.Cout, pk.KH, pk.KW, B, H, W))
-        return out
+        args = (_p(z), _p(pk.bias) if pk.bias is not None else None, _p(e0) if e0 is not None else None, e0_bs, _p(out), out_bs,
+                B, pk.Cout, H, W, pk.KH, pk.KW, pk.padH, pk.padW, int(act), int(epi))
+        _launch(lib.accflow_tap_sum_f32, args, "accflow_tap_sum_f32",
+                ("conv2d", lambda: (0.0, "tap_sum Cout%d k%dx%d B%d %dx%d" % (pk.Cout, pk.KH, pk.KW, B, H, W))))
+        return out, None
     if offset is not None and pk.zcols is not None and md != CONV_F32 and in1 is None:
         # deformable conv in two passes: deformed im2col columns (memory-bound), then a 1x1 conv on the matrix cores
-        B, C, H, W = in0.shape
-        cols = torch.empty((B, pk.KH * pk.KW * C, H, W), dtype=torch.float32, device=in0.device)
-        tm = profiler.ACTIVE
-        t0 = tm.begin() if tm is not None and tm.wants("conv2d") else None
-        _check(lib.accflow_deform_columns_f32(_p(in0), _plane4(in0, "in0"), _p(offset), _plane4(offset, "offset"), _p(dmask),
-                                              _plane4(dmask, "dmask"), _p(cols), B, C, H, W, pk.KH, pk.KW, pk.padH, pk.padW,
-                                              _stream()), "accflow_deform_columns_f32")
-        if t0 is not None:
-            tm.end("conv2d", t0, 0.0, "deform_columns C%d k%dx%d B%d %dx%d" % (C, pk.KH, pk.KW, B, H, W))
-        return conv2d(pk.zcols, cols, out=out, act=act, epi=epi, e0=e0, e1=e1, out2=out2, mode=md)
-    d = ConvDesc()
-    d.in0_bs = _plane4(in0, "in0")
-    B, C0, H, W = in0.shape
-    C1 = 0
-    if in1 is not None:
-        d.in1_bs = _plane4(in1, "in1")
-        if in1.shape[0] != B or in1.shape[2:] != in0.shape[2:]:
-            raise RuntimeError("conv2d: in0/in1 shape mismatch")
-        C1 = in1.shape[1]
-    if C0 != pk.C0 or C0 + C1 != pk.Cin:
-        raise RuntimeError("conv2d: channel split (%d,%d) does not match packed weights (C0=%d, Cin=%d)"
-                           % (C0, C1, pk.C0, pk.Cin))
-    OH, OW = pk.out_size(H, W)
-    if out is None:
-        out = torch.empty((B, pk.Cout, OH, OW), dtype=torch.float32, device=in0.device)
-    d.out_bs = _plane4(out, "out")
-    n_out = pk.Cout // 2 if epi == EPI_GRU_ZR else pk.Cout
-    if tuple(out.shape) != (B, n_out, OH, OW):
-        raise RuntimeError("conv2d: out shape %s != %s" % (tuple(out.shape), (B, n_out, OH, OW)))
-    d.in0, d.in1 = in0.data_ptr(), (in1.data_ptr() if in1 is not None else None)
-    d.C0, d.C1, d.B, d.H, d.W, d.OH, d.OW = C0, C1, B, H, W, OH, OW
-    d.KH, d.KW, d.stride, d.padH, d.padW, d.Cout = pk.KH, pk.KW, pk.stride, pk.padH, pk.padW, pk.Cout
-    d.wpack, d.ktab, d.Kpad, d.CoutPad = pk.wpack.data_ptr(), pk.ktab.data_ptr(), pk.Kpad, pk.CoutPad
-    d.bias = pk.bias.data_ptr() if pk.bias is not None else None
-    d.out, d.act, d.epi = out.data_ptr(), act, epi
-    d.mode = md
-    d.wsplit = pk.wsplit.data_ptr() if pk.wsplit is not None else None
-    d.wpatch = pk.wpatch.data_ptr() if (pk.wpatch is not None and USE_PATCH) else None
-    if d.mode == CONV_F16X3 and pk.wscale16 is not None:
-        if d.wpatch and pk.wpatch16 is not None:
-            d.wpatch16 = pk.wpatch16.data_ptr()
-        if pk.wsplit16 is not None:
-            d.wsplit16 = pk.wsplit16.data_ptr()
-        d.wscale16 = pk.wscale16.data_ptr()
-        d.guard = _guard(in0.device).data_ptr()
-    if d.wpatch and _ksplit_on() and B * OH * OW <= KSPLIT_MAX_PIXELS and pk.Cout > 4:
-        # small grids (the batch-1 fusion chain): scratch for 4 K-parts, summed by a second kernel
-        ws = _ksplit_ws(4 * B * pk.Cout * OH * OW, in0.device)
-        d.kws, d.kws_elems = ws.data_ptr(), ws.numel()
-    if e0 is not None:
-        d.e0_bs = _plane4(e0, "e0")
-        d.e0 = e0.data_ptr()
-    if e1 is not None:
-        d.e1_bs = _plane4(e1, "e1")
-        d.e1 = e1.data_ptr()
-    if out2 is not None:
-        d.out2_bs = _plane4(out2, "out2")
-        d.out2 = out2.data_ptr()
-    if pre is not None:  # pre-activation addend of the GRU epilogues, (B, Cout, OH, OW)
-        if epi not in (EPI_GRU_ZR, EPI_GRU_Q) or tuple(pre.shape) != (B, pk.Cout, OH, OW):
-            raise RuntimeError("conv2d: `pre` is a (B, Cout, OH, OW) addend of the GRU epilogues")
-        d.pre_bs = _plane4(pre, "pre")
-        d.pre = pre.data_ptr()
-    if offset is not None:
-        d.offset_bs = _plane4(offset, "offset")
-        d.offset = offset.data_ptr()
-        d.dmask_bs = _plane4(dmask, "dmask")
-        d.dmask = dmask.data_ptr()
-        if not pk.tap_major:
-            raise RuntimeError("deformable conv needs tap-major packed weights")
-    if in_norm is not None:
-        # in0 = the raw output of a convolution; in_norm = its (B, C0, 2) {mean, rstd} (instance_stats_finalize): the
-        # kernel reads relu((x - mean) * rstd).  None is returned if the kernel chosen for this call cannot do that.
-        if in1 is not None or tuple(_dense(in_norm, "in_norm").shape) != (B, C0, 2):
-            raise RuntimeError("conv2d: in_norm is (B, C0, 2) for a single-source input")
-        if not lib.accflow_conv_in_norm_supported(ctypes.byref(d)):
-            return None
-        d.in_norm = in_norm.data_ptr()
-    if stats_holder is not None and USE_NORM_STATS:
-        slots = lib.accflow_conv_stat_slots(ctypes.byref(d))
-        if slots > 0:
-            st = ConvStats(torch.empty((B, pk.Cout, slots, 3), dtype=torch.float32, device=in0.device), slots)
-            d.stats, d.stat_slots = st.partial.data_ptr(), slots
-            stats_holder.append(st)
-    tm = profiler.ACTIVE
-    if tm is not None and tm.wants("conv2d"):
-        t0 = tm.begin()
-        _check(lib.accflow_conv2d_f32(ctypes.byref(d), _stream()), "accflow_conv2d_f32")
-        acin = pk.Cin if algo_cin is None else algo_cin
-        tm.end("conv2d", t0, 2.0 * acin * pk.KH * pk.KW * pk.Cout * B * OH * OW,  # algorithmic flop
-               "Cin%d Cout%d k%dx%d s%d B%d %dx%d%s%s" % (pk.Cin, pk.Cout, pk.KH, pk.KW, pk.stride, B, OH, OW,
-                                                         " deform" if offset is not None else "",
-                                                         "" if algo_cin is None else " (stands for Cin%d)" % algo_cin),
-               work_exec=2.0 * pk.Cin * pk.KH * pk.KW * pk.Cout * B * OH * OW)
-        return out
-    _check(lib.accflow_conv2d_f32(ctypes.byref(d), _stream()), "accflow_conv2d_f32")
-    return out
+        cols = _deform_columns(pk, in0, offset, dmask)
+        return conv2d(pk.zcols, cols, out=out, act=act, epi=epi, e0=e0, e1=e1, out2=out2, mode=md), None
+    # split-K: only beside the direct kernel's patch pack
+    b = _conv_desc(_FORM_F32, pk, (in0, in1), act, epi, md, out, e0=e0, e1=e1, out2=out2, pre=pre, offset=offset, dmask=dmask,
+                   in_norm=in_norm, stats=want_stats and USE_NORM_STATS, kws_ok=pk.wpatch is not None and USE_PATCH)
+    if b is None:
+        return None
+    d, ret, st, _ = b
+    _launch(lib.accflow_conv2d_f32, (ctypes.byref(d),), "accflow_conv2d_f32",
+            ("conv2d", lambda: _conv_figures(pk, d, " deform" if offset is not None else "", algo_cin)))
+    return ret, st
 
 
-def _conv2d_s16(pk, in0, in1, out, act, epi, e0, e1, out2, mode, pre, algo_cin, out16, fp32_out, cache=None, p32_out=False):
-    lib = _lib.load()
-    md = current_mode() if mode is None else mode
-    if md != CONV_F16X3 or (pk.wpatch16 is None and pk.wsplit16 is None):
-        raise RuntimeError("conv2d: S16 tensors need the f16x3 mode and a direct-kernel weight pack")
-    d = ConvDesc()
-    fmt = 0
-    srcs = []
-    for k, t in enumerate((in0, in1)):
-        if t is None:
-            srcs.append((None, 0, 0))
-        elif isinstance(t, S16):
-            fmt |= 1 << k
-            srcs.append((t.ptr(), t.bs, t.C))
-        else:
-            srcs.append((t.data_ptr(), _plane4(t, "in%d" % k), t.shape[1]))
-    if fmt and fmt != (3 if in1 is not None else 1):
-        raise RuntimeError("conv2d: both sources must have the same format")
-    B, _, H, W = in0.shape
-    if in1 is not None and (in1.shape[0] != B or tuple(in1.shape[2:]) != (H, W)):
-        raise RuntimeError("conv2d: in0/in1 shape mismatch")
-    C0, C1 = srcs[0][2], srcs[1][2]
-    if C0 != pk.C0 or C0 + C1 != pk.Cin:
-        raise RuntimeError("conv2d: channel split (%d,%d) does not match packed weights (C0=%d, Cin=%d)" % (C0, C1, pk.C0, pk.Cin))
-    OH, OW = pk.out_size(H, W)
-    n_out = pk.Cout // 2 if epi == EPI_GRU_ZR else pk.Cout
-    dev = in0.data.device if isinstance(in0, S16) else in0.device
-    if out is None and (fp32_out or epi == EPI_GRU_ZR):
-        out = torch.empty((B, n_out, OH, OW), dtype=torch.float32, device=dev)
-    if out is not None:
-        d.out_bs = _plane4(out, "out")
-        if tuple(out.shape) != (B, n_out, OH, OW):
-            raise RuntimeError("conv2d: out shape %s != %s" % (tuple(out.shape), (B, n_out, OH, OW)))
-        d.out = out.data_ptr()
-    if out16 is not None:
-        if tuple(out16.shape) != (B, n_out, OH, OW):
-            raise RuntimeError("conv2d: out16 shape %s != %s" % (out16.shape, (B, n_out, OH, OW)))
-        d.out16, d.out16_bs = out16.ptr(), out16.bs
-    d.in0, d.in0_bs = srcs[0][0], srcs[0][1]
-    d.in1, d.in1_bs = srcs[1][0], srcs[1][1]
-    d.in_fmt = fmt
-    if S16_VIA_MULTI and fmt:
-        # the same convolution through the multi-source kernel (same pack, same results; per-call switch for A/B runs)
-        d.nsrc = 2 if in1 is not None else 1
-        for k in range(d.nsrc):
-            S = d.src[k]
-            S.ptr, S.bs, S.C, S.Hs, S.Ws = srcs[k][0], srcs[k][1], srcs[k][2], H, W
-            S.step, S.oy, S.ox, S.KH, S.KW, S.padH, S.padW = 1, 0, 0, pk.KH, pk.KW, pk.padH, pk.padW
-    d.C0, d.C1, d.B, d.H, d.W, d.OH, d.OW = C0, C1, B, H, W, OH, OW
-    d.KH, d.KW, d.stride, d.padH, d.padW, d.Cout = pk.KH, pk.KW, pk.stride, pk.padH, pk.padW, pk.Cout
-    d.wpack, d.ktab, d.Kpad, d.CoutPad = pk.wpack.data_ptr(), pk.ktab.data_ptr(), pk.Kpad, pk.CoutPad
-    d.bias = pk.bias.data_ptr() if pk.bias is not None else None
-    d.act, d.epi, d.mode = act, epi, md
-    d.wsplit = pk.wsplit.data_ptr() if pk.wsplit is not None else None
-    if pk.wpatch16 is not None:
-        d.wpatch, d.wpatch16 = pk.wpatch.data_ptr(), pk.wpatch16.data_ptr()
-    if pk.wsplit16 is not None:     # (the stem kernel - 7x7 stride 2 of the image, S16 output - reads the im2col fp16 pack)
-        d.wsplit16 = pk.wsplit16.data_ptr()
-    d.wscale16 = pk.wscale16.data_ptr()
-    d.guard = _guard(dev).data_ptr()
-    ws_keep = None
-    if _ksplit_on() and B * OH * OW <= KSPLIT_MAX_PIXELS and pk.Cout > 4 and not isinstance(e0, S16) and not p32_out:
-        ws_keep = _ksplit_ws(4 * B * pk.Cout * OH * OW, dev)    # small grids: see _conv2d
-        d.kws, d.kws_elems = ws_keep.data_ptr(), ws_keep.numel()
-    if isinstance(e0, S16):
-        # the GRU state kept pre-split only (accflow_conv_desc.e0_fmt, GRU_ZR / GRU_Q of the 5-tap convolutions): the epilogue
-        # reads h = (hi + lo) / 2^4 with 8-byte block loads
-        if epi not in (EPI_GRU_ZR, EPI_GRU_Q) or tuple(e0.shape) != (B, n_out, OH, OW):
-            raise RuntimeError("conv2d: an S16 e0 is the GRU epilogues' state operand, shape (B, hidden, OH, OW)")
-        d.e0_bs, d.e0, d.e0_fmt = e0.bs, e0.ptr(), 1
-        d.p32 = 3 if epi == EPI_GRU_ZR else 6      # z out + pre / pre + e1 (z) in the pixel-major layout
-    elif e0 is not None:
-        d.e0_bs, d.e0 = _plane4(e0, "e0"), e0.data_ptr()
-    if e1 is not None:
-        d.e1_bs, d.e1 = _plane4(e1, "e1"), e1.data_ptr()
-    if out2 is not None:
-        d.out2_bs, d.out2 = _plane4(out2, "out2"), out2.data_ptr()
-    if pre is not None:
-        if epi not in (EPI_GRU_ZR, EPI_GRU_Q) or tuple(pre.shape) != (B, pk.Cout, OH, OW):
-            raise RuntimeError("conv2d: `pre` is a (B, Cout, OH, OW) addend of the GRU epilogues")
-        d.pre_bs, d.pre = _plane4(pre, "pre"), pre.data_ptr()
-    if p32_out:
-        if epi != EPI_STORE or out is None or pk.Cout % 128 or isinstance(e0, S16):
-            raise RuntimeError("conv2d: p32_out is a plain fp32 store onto a multiple of 128 channels")
-        d.p32 = 1
-    tm = profiler.ACTIVE
-    t0 = tm.begin() if tm is not None and tm.wants("conv2d") else None
-    _check(lib.accflow_conv2d_f32(ctypes.byref(d), _stream()), "accflow_conv2d_f32 (S16)")
-    if t0 is not None:
-        acin = pk.Cin if algo_cin is None else algo_cin
-        tm.end("conv2d", t0, 2.0 * acin * pk.KH * pk.KW * pk.Cout * B * OH * OW,
-               "Cin%d Cout%d k%dx%d s%d B%d %dx%d S16%s%s" % (pk.Cin, pk.Cout, pk.KH, pk.KW, pk.stride, B, OH, OW,
-                                                            "in" if fmt else "", "" if algo_cin is None else " (stands for Cin%d)" % algo_cin),
-               work_exec=2.0 * pk.Cin * pk.KH * pk.KW * pk.Cout * B * OH * OW)
-    ret = out if (out is not None and (fp32_out or out16 is None)) else out16
-    if cache is not None and profiler.ACTIVE is None:   # (the predicate conv2d() replays under)
-        # the entry keeps every tensor the descriptor points at alive: the pack, the S16 / fp32 operands, and the
-        # split-K scratch d.kws points into (_ksplit_ws drops its buffer when a later conv asks for a larger one)
-        cache[0][cache[1]] = (d, ret, (pk, in0, in1, out, out16, e0, e1, out2, pre, ws_keep))
-    return ret
+def _deform_columns(pk, x, offset, dmask, name="in0"):
+    """fp32 deformed im2col columns (B, KH*KW*C, H, W) of x (accflow_deform_columns_f32)."""
+    B, C, H, W = x.shape
+    cols = torch.empty((B, pk.KH * pk.KW * C, H, W), dtype=torch.float32, device=x.device)
+    args = (_p(x), _plane4(x, name), _p(offset), _plane4(offset, "offset"), _p(dmask), _plane4(dmask, "dmask"), _p(cols),
+            B, C, H, W, pk.KH, pk.KW, pk.padH, pk.padW)
+    _launch(_lib.load().accflow_deform_columns_f32, args, "accflow_deform_columns_f32",
+            ("conv2d", lambda: (0.0, "deform_columns C%d k%dx%d B%d %dx%d" % (C, pk.KH, pk.KW, B, H, W))))
+    return cols
 
 
 
@@ -772,14 +819,11 @@ def conv2d_tapgemm(pk1, pk2, in0, in1=None, out=None, epi=EPI_STORE, e0=None, ca
     with the ACCFLOW_EPI_TAPGEMM epilogue (its output never reaches HBM: the workgroup multiplies it by conv2's tap matrix and
     writes 18 rows per pixel and 128-channel block), then accflow_tap_sum_parts_f32 (adds the blocks, shifts and sums the
     taps, bias, epilogue).  Same arithmetic as the three-launch form up to the order of the fp32 sums over conv1's channels.
-    cache = (dict, key): replay protocol of conv2d (pass pk1 = None to replay)."""
-    lib = _lib.load()
-    if cache is not None and profiler.ACTIVE is None:
-        hit = cache[0].get(cache[1])
-        if hit is not None:
-            _check(lib.accflow_conv2d_f32(ctypes.byref(hit[0]), _stream()), "accflow_conv2d_f32 (tapgemm, cached)")
-            _check(lib.accflow_tap_sum_parts_f32(*hit[2], _stream()), "accflow_tap_sum_parts_f32 (cached)")
-            return hit[1]
+    cache = (dict, key): replay protocol of conv2d (pass pk1 = None to replay); the first launch is kept under `key`, the tap
+    sum under (key, "tap_sum")."""
+    cache2 = (cache[0], (cache[1], "tap_sum")) if cache is not None else None
+    if _replay(cache, "accflow_conv2d_f32 (tapgemm)") is not None:
+        return _replay(cache2, "accflow_tap_sum_parts_f32")
     if pk1 is None:
         raise RuntimeError("conv2d_tapgemm: no packed weights given and no cached descriptor for %r to replay"
                            % (cache[1] if cache is not None else None,))
@@ -787,49 +831,29 @@ def conv2d_tapgemm(pk1, pk2, in0, in1=None, out=None, epi=EPI_STORE, e0=None, ca
         raise RuntimeError("conv2d_tapgemm: shapes / mode outside the fused form (ops.tapgemm_eligible)")
     if epi not in (EPI_STORE, EPI_ACCUM, EPI_RES_RELU) or (epi != EPI_STORE and e0 is None):
         raise RuntimeError("conv2d_tapgemm: epi is STORE, ACCUM (+ e0) or RES_RELU (+ e0)")
+    lib = _lib.load()
     B, _, H, W = in0.shape
-    C0, C1 = in0.C, (in1.C if in1 is not None else 0)
-    if C0 != pk1.C0 or C0 + C1 != pk1.Cin:
-        raise RuntimeError("conv2d_tapgemm: channel split (%d,%d) does not match packed weights" % (C0, C1))
-    dev = in0.data.device
+    dev = in0.device
     pz = pk2.ztaps_acc
     rows, nparts = pz.Cout, pk1.Cout // 128
     z = torch.empty((nparts, B, rows, H, W), dtype=torch.float32, device=dev)
     if out is None:
         out = torch.empty((B, pk2.Cout, H, W), dtype=torch.float32, device=dev)
-    d = ConvDesc()
-    d.in0, d.in0_bs = in0.ptr(), in0.bs
-    if in1 is not None:
-        d.in1, d.in1_bs = in1.ptr(), in1.bs
-    d.in_fmt = 3 if in1 is not None else 1
-    d.C0, d.C1, d.B, d.H, d.W, d.OH, d.OW = C0, C1, B, H, W, H, W
-    d.KH, d.KW, d.stride, d.padH, d.padW, d.Cout = pk1.KH, pk1.KW, 1, pk1.padH, pk1.padW, pk1.Cout
-    d.wpack, d.ktab, d.Kpad, d.CoutPad = pk1.wpack.data_ptr(), pk1.ktab.data_ptr(), pk1.Kpad, pk1.CoutPad
-    d.bias = pk1.bias.data_ptr() if pk1.bias is not None else None
-    d.act, d.epi, d.mode = ACT_RELU, EPI_TAPGEMM, CONV_F16X3
-    d.wpatch, d.wpatch16, d.wscale16 = pk1.wpatch.data_ptr(), pk1.wpatch16.data_ptr(), pk1.wscale16.data_ptr()
-    d.guard = _guard(dev).data_ptr()
-    d.tg_w16, d.tg_scale, d.tg_out = pz.wpatch16.data_ptr(), pz.wscale16.data_ptr(), z.data_ptr()
-    d.tg_out_bs, d.tg_out_ps, d.tg_rows, d.tg_coutpad = rows * H * W, B * rows * H * W, rows, pz.CoutPad
+    # (eligible shapes: stride 1 and "same" padding, so the descriptor's geometry is the pack's; never a split-K workspace;
+    # `out` and `e0` are the tap sum's, not the descriptor's)
+    d, _, _, keep = _conv_desc(_FORM_TAPGEMM, pk1, (in0, in1), ACT_RELU, EPI_TAPGEMM, CONV_F16X3, tg=(pz, z), kws_ok=False)
     out_bs = _plane4(out, "out")
     e0_bs = _plane4(e0, "e0") if e0 is not None else 0
     targs = (z.data_ptr(), nparts, B * rows * H * W, rows * H * W, _p(pk2.bias) if pk2.bias is not None else None,
              _p(e0) if e0 is not None else None, e0_bs, _p(out), out_bs, B, pk2.Cout, H, W, pk2.KH, pk2.KW, pk2.padH, pk2.padW,
              int(ACT_NONE), int(epi))
-    tm = profiler.ACTIVE
-    t0 = tm.begin() if tm is not None and tm.wants("conv2d") else None
-    _check(lib.accflow_conv2d_f32(ctypes.byref(d), _stream()), "accflow_conv2d_f32 (tapgemm)")
-    if t0 is not None:
-        px = B * H * W
-        tm.end("conv2d", t0, 2.0 * (pk1.Cin * pk1.KH * pk1.KW * pk1.Cout + pk1.Cout * rows) * px,
-               "Cin%d Cout%d k%dx%d s1 B%d %dx%d S16in +tapgemm%d" % (pk1.Cin, pk1.Cout, pk1.KH, pk1.KW, B, H, W, rows))
-        t0 = tm.begin()
-    _check(lib.accflow_tap_sum_parts_f32(*targs, _stream()), "accflow_tap_sum_parts_f32")
-    if t0 is not None:
-        tm.end("conv2d", t0, 0.0, "tap_sum Cout%d k%dx%d B%d %dx%d (%d parts)" % (pk2.Cout, pk2.KH, pk2.KW, B, H, W, nparts))
-    if cache is not None and profiler.ACTIVE is None:
-        cache[0][cache[1]] = (d, out, targs, (pk1, pk2, in0, in1, out, e0, z))
-    return out
+    _launch(lib.accflow_conv2d_f32, (ctypes.byref(d),), "accflow_conv2d_f32 (tapgemm)",
+            ("conv2d", lambda: (2.0 * (pk1.Cin * pk1.KH * pk1.KW * pk1.Cout + pk1.Cout * rows) * (B * H * W),
+                                "Cin%d Cout%d k%dx%d s1 B%d %dx%d S16in +tapgemm%d" % (pk1.Cin, pk1.Cout, pk1.KH, pk1.KW, B, H, W, rows))),
+            cache, out, keep)
+    return _launch(lib.accflow_tap_sum_parts_f32, targs, "accflow_tap_sum_parts_f32",
+                   ("conv2d", lambda: (0.0, "tap_sum Cout%d k%dx%d B%d %dx%d (%d parts)" % (pk2.Cout, pk2.KH, pk2.KW, B, H, W, nparts))),
+                   cache2, out, (pk2, out, e0, z))
 
 
 class PackedMulti:
@@ -952,81 +976,23 @@ def conv2d_multi(pk, srcs, out=None, act=ACT_NONE, epi=EPI_STORE, e0=None, e1=No
     """Multi-source S16 convolution: srcs[s] = the ops.S16 tensor read as source s of `pk` (a PackedMulti; the same tensor
     may appear several times - the parity classes of a strided conv).  out_hw: output size (default: the first source's
     size divided by its step, rounded up).  Other arguments as conv2d; want_stats returns (out, ConvStats or None)."""
-    lib = _lib.load()
     if current_mode() != CONV_F16X3:
         raise RuntimeError("conv2d_multi: S16 tensors need the f16x3 mode")
     if len(srcs) != len(pk.C):
         raise RuntimeError("conv2d_multi: %d sources for a %d-source pack" % (len(srcs), len(pk.C)))
-    d = ConvDesc()
-    B = srcs[0].shape[0]
+    if want_stats and (act != ACT_NONE or epi != EPI_STORE):
+        raise RuntimeError("conv2d_multi: statistics are gathered for plain convolutions only (store, no activation)")
     if out_hw is None:
         st = pk.geo[0][0]
         out_hw = ((srcs[0].shape[2] + st - 1) // st, (srcs[0].shape[3] + st - 1) // st)
-    OH, OW = int(out_hw[0]), int(out_hw[1])
-    d.nsrc = len(srcs)
-    for k, (t, c, g) in enumerate(zip(srcs, pk.C, pk.geo)):
-        if not isinstance(t, S16) or t.C != c or t.shape[0] != B:
-            raise RuntimeError("conv2d_multi: source %d must be an ops.S16 of %d channels and batch %d" % (k, c, B))
-        S = d.src[k]
-        S.ptr, S.bs, S.C, S.Hs, S.Ws = t.ptr(), t.bs, c, t.shape[2], t.shape[3]
-        S.step, S.oy, S.ox, S.KH, S.KW, S.padH, S.padW = g
-    if lay is not None:
-        d.src[0].reserved = int(lay) + 1      # tests / tuning: force a wave layout
-    dev = srcs[0].device
-    n_out = pk.Cout // 2 if epi == EPI_GRU_ZR else pk.Cout
-    if out is None and (fp32_out or epi == EPI_GRU_ZR or out16 is None):
-        out = torch.empty((B, n_out, OH, OW), dtype=torch.float32, device=dev)
-    if out is not None:
-        d.out_bs = _plane4(out, "out")
-        if tuple(out.shape) != (B, n_out, OH, OW):
-            raise RuntimeError("conv2d_multi: out shape %s != %s" % (tuple(out.shape), (B, n_out, OH, OW)))
-        d.out = out.data_ptr()
-    if out16 is not None:
-        if tuple(out16.shape) != (B, n_out, OH, OW):
-            raise RuntimeError("conv2d_multi: out16 shape %s != %s" % (out16.shape, (B, n_out, OH, OW)))
-        d.out16, d.out16_bs = out16.ptr(), out16.bs
-    d.B, d.H, d.W, d.OH, d.OW, d.Cout, d.CoutPad = B, OH, OW, OH, OW, pk.Cout, pk.CoutPad
-    d.split_c0 = pk.split_c0
-    d.KH = d.KW = d.stride = 1
-    d.bias = pk.bias.data_ptr() if pk.bias is not None else None
-    d.act, d.epi, d.mode = act, epi, CONV_F16X3
-    d.wpatch16, d.wscale16 = pk.wpatch16.data_ptr(), pk.wscale16.data_ptr()
-    d.guard = _guard(dev).data_ptr()
-    if _ksplit_on() and B * OH * OW <= KSPLIT_MAX_PIXELS and pk.Cout > 4 and not want_stats and not pk.split_c0:
-        ws = _ksplit_ws(4 * B * pk.Cout * OH * OW, dev)
-        d.kws, d.kws_elems = ws.data_ptr(), ws.numel()
-    if isinstance(e0, S16):     # residual operand kept pre-split only (the encoders' block input)
-        if tuple(e0.shape) != (B, pk.Cout, OH, OW):
-            raise RuntimeError("conv2d_multi: S16 e0 shape %s != %s" % (e0.shape, (B, pk.Cout, OH, OW)))
-        d.e0_bs, d.e0, d.e0_fmt = e0.bs, e0.ptr(), 1
-        d.kws, d.kws_elems = None, 0
-    elif e0 is not None:
-        d.e0_bs, d.e0 = _plane4(e0, "e0"), e0.data_ptr()
-    if e1 is not None:
-        d.e1_bs, d.e1 = _plane4(e1, "e1"), e1.data_ptr()
-    if out2 is not None:
-        d.out2_bs, d.out2 = _plane4(out2, "out2"), out2.data_ptr()
-    if pre is not None:
-        if epi not in (EPI_GRU_ZR, EPI_GRU_Q) or tuple(pre.shape) != (B, pk.Cout, OH, OW):
-            raise RuntimeError("conv2d_multi: `pre` is a (B, Cout, OH, OW) addend of the GRU epilogues")
-        d.pre_bs, d.pre = _plane4(pre, "pre"), pre.data_ptr()
-    stats = None
-    if want_stats:
-        if act != ACT_NONE or epi != EPI_STORE:
-            raise RuntimeError("conv2d_multi: statistics are gathered for plain convolutions only (store, no activation)")
-        slots = lib.accflow_conv_stat_slots(ctypes.byref(d))
-        if slots > 0:
-            stats = ConvStats(torch.empty((B, pk.Cout, slots, 3), dtype=torch.float32, device=dev), slots)
-            d.stats, d.stat_slots = stats.partial.data_ptr(), slots
-    tm = profiler.ACTIVE
-    t0 = tm.begin() if tm is not None and tm.wants("conv2d") else None
-    _check(lib.accflow_conv2d_f32(ctypes.byref(d), _stream()), "accflow_conv2d_f32 (multi-source S16)")
-    if t0 is not None:
-        g0 = pk.geo[0]
-        tm.end("conv2d", t0, pk.flop_per_px * B * OH * OW,
-               "multi[%s] Cout%d step%d B%d %dx%d" % ("+".join("%dx%dx%d" % (c, g[3], g[4]) for c, g in zip(pk.C, pk.geo)),
-                                                    pk.Cout, g0[0], B, OH, OW))
-    ret = out if (out is not None and (fp32_out or out16 is None)) else out16
+    # split-K: not with statistics, not for a pack with a projection; statistics: USE_NORM_STATS is not consulted here
+    d, ret, stats, _ = _conv_desc(_FORM_MULTI, pk, srcs, act, epi, CONV_F16X3, out, out16, fp32_out, e0, e1, out2, pre,
+                                  stats=want_stats, kws_ok=not want_stats and not pk.split_c0,
+                                  out_hw=(int(out_hw[0]), int(out_hw[1])), lay=lay)
+    _launch(_lib.load().accflow_conv2d_f32, (ctypes.byref(d),), "accflow_conv2d_f32 (multi-source S16)",
+            ("conv2d", lambda: (pk.flop_per_px * d.B * d.OH * d.OW,
+                                "multi[%s] Cout%d step%d B%d %dx%d" % ("+".join("%dx%dx%d" % (c, g[3], g[4]) for c, g in zip(pk.C, pk.geo)),
+                                                                     pk.Cout, pk.geo[0][0], d.B, d.OH, d.OW))))
     return (ret, stats) if want_stats else ret
 
 
@@ -1038,27 +1004,20 @@ def deform_conv2d_s16(pk, x, offset, dmask, out16, mask_is_logit=False):
     the deformed im2col columns, then the 1x1 matrix-core convolution over them writing the ops.S16 tensor `out16` only.
     Round 6: the columns themselves are written pre-split (accflow_deform_columns_s16: the 1x1 convolution stages them by LDS
     DMA), and with mask_is_logit the modulation's sigmoid (AccFlow_.py:103) is applied while sampling."""
-    lib = _lib.load()
     if pk.zcols is None:
         raise RuntimeError("deform_conv2d_s16: needs a tap-major pack with the column form (stride 1)")
     B, C, H, W = x.shape
-    tm = profiler.ACTIVE
-    t0 = tm.begin() if tm is not None and tm.wants("conv2d") else None
     if USE_DEFORM_S16_COLUMNS and C % 8 == 0 and (pk.KH * pk.KW * C) % 32 == 0:
         cols = S16.empty(B, pk.KH * pk.KW * C, H, W, x.device)
-        _check(lib.accflow_deform_columns_s16(_p(x), _plane4(x, "x"), _p(offset), _plane4(offset, "offset"), _p(dmask),
-                                              _plane4(dmask, "dmask"), int(bool(mask_is_logit)), ctypes.c_void_p(cols.ptr()), cols.bs,
-                                              _p(_guard(x.device)), B, C, H, W, pk.KH, pk.KW, pk.padH, pk.padW, _stream()),
-               "accflow_deform_columns_s16")
+        args = (_p(x), _plane4(x, "x"), _p(offset), _plane4(offset, "offset"), _p(dmask), _plane4(dmask, "dmask"),
+                int(bool(mask_is_logit)), ctypes.c_void_p(cols.ptr()), cols.bs, _p(_guard(x.device)),
+                B, C, H, W, pk.KH, pk.KW, pk.padH, pk.padW)
+        _launch(_lib.load().accflow_deform_columns_s16, args, "accflow_deform_columns_s16",
+                ("conv2d", lambda: (0.0, "deform_columns C%d k%dx%d B%d %dx%d" % (C, pk.KH, pk.KW, B, H, W))))
     else:
         if mask_is_logit:
             dmask = activation_(dmask, ACT_SIGMOID)
-        cols = torch.empty((B, pk.KH * pk.KW * C, H, W), dtype=torch.float32, device=x.device)
-        _check(lib.accflow_deform_columns_f32(_p(x), _plane4(x, "x"), _p(offset), _plane4(offset, "offset"), _p(dmask),
-                                              _plane4(dmask, "dmask"), _p(cols), B, C, H, W, pk.KH, pk.KW, pk.padH, pk.padW,
-                                              _stream()), "accflow_deform_columns_f32")
-    if t0 is not None:
-        tm.end("conv2d", t0, 0.0, "deform_columns C%d k%dx%d B%d %dx%d" % (C, pk.KH, pk.KW, B, H, W))
+        cols = _deform_columns(pk, x, offset, dmask, "x")
     return conv2d(pk.zcols, cols, out16=out16, fp32_out=False)
 
 
@@ -1295,15 +1254,10 @@ def corr_lookup_alt(pairs, coords, out=None, cache=None):
     out_bs = _plane4(out, "out")
     if tuple(out.shape) != (B, 324, H8, W8):
         raise RuntimeError("corr_lookup_alt: out shape %s" % (tuple(out.shape),))
-    tm = profiler.ACTIVE
-    t0 = tm.begin() if tm is not None and tm.wants("corr_lookup") else None
     args = (_p(p.data), p.F, _p(pairs.idx), _p(coords), _p(out), out_bs, B, p.C, H8, W8)
-    _check(lib.accflow_corr_lookup_alt_f32(*args, _stream()), "accflow_corr_lookup_alt_f32")
-    if t0 is not None:
-        tm.end("corr_lookup", t0, LOOKUP_BYTES_PER_PX * B * H8 * W8, "alt B%d %dx%d" % (B, H8, W8))
-    elif cache is not None and tm is None:
-        cache[0][cache[1]] = (lib.accflow_corr_lookup_alt_f32, args, out, (pairs, coords, out))
-    return out
+    return _launch(lib.accflow_corr_lookup_alt_f32, args, "accflow_corr_lookup_alt_f32",
+                   ("corr_lookup", lambda: (LOOKUP_BYTES_PER_PX * B * H8 * W8, "alt B%d %dx%d" % (B, H8, W8))),
+                   cache, out, (pairs, coords, out))
 
 
 def corr_lookup_alt_s16(pairs, coords, out16, cache=None):
@@ -1317,16 +1271,11 @@ def corr_lookup_alt_s16(pairs, coords, out16, cache=None):
     B, H8, W8 = pairs.B, p.H8, p.W8
     if tuple(out16.shape) != (B, LOOKUP_S16_CHANNELS, H8, W8):
         raise RuntimeError("corr_lookup_alt_s16: shape mismatch")
-    tm = profiler.ACTIVE
-    t0 = tm.begin() if tm is not None and tm.wants("corr_lookup") else None
     args = (_p(p.data), p.F, _p(pairs.idx), _p(coords), ctypes.c_void_p(out16.ptr()), out16.bs, _p(_guard(coords.device)),
             B, p.C, H8, W8)
-    _check(lib.accflow_corr_lookup_alt_s16(*args, _stream()), "accflow_corr_lookup_alt_s16")
-    if t0 is not None:
-        tm.end("corr_lookup", t0, LOOKUP_BYTES_PER_PX * B * H8 * W8, "alt s16 B%d %dx%d" % (B, H8, W8))
-    elif cache is not None and tm is None:
-        cache[0][cache[1]] = (lib.accflow_corr_lookup_alt_s16, args, out16, (pairs, coords, out16))
-    return out16
+    return _launch(lib.accflow_corr_lookup_alt_s16, args, "accflow_corr_lookup_alt_s16",
+                   ("corr_lookup", lambda: (LOOKUP_BYTES_PER_PX * B * H8 * W8, "alt s16 B%d %dx%d" % (B, H8, W8))),
+                   cache, out16, (pairs, coords, out16))
 
 
 def corr_lookup(pyramid, coords, out=None):
@@ -1345,13 +1294,8 @@ def _corr_lookup_alt(pyr, coords, out, entry):
         out = torch.empty((B, 324, H8, W8), dtype=torch.float32, device=coords.device)
     out_bs = _plane4(out, "out")
     lv = pyr.levels
-    tm = profiler.ACTIVE
-    t0 = tm.begin() if tm is not None and tm.wants("corr_lookup") else None
-    _check(getattr(lib, entry)(_p(lv[0]), _p(lv[1]), _p(lv[2]), _p(lv[3]), _p(coords), _p(out), out_bs,
-                               B, H8, W8, _stream()), entry)
-    if t0 is not None:
-        tm.end("corr_lookup", t0, LOOKUP_BYTES_PER_PX * B * H8 * W8)
-    return out
+    return _launch(getattr(lib, entry), (_p(lv[0]), _p(lv[1]), _p(lv[2]), _p(lv[3]), _p(coords), _p(out), out_bs, B, H8, W8),
+                   entry, ("corr_lookup", lambda: (LOOKUP_BYTES_PER_PX * B * H8 * W8,)), ret=out)
 
 
 def to_s16(src, dst16=None):
@@ -1366,18 +1310,6 @@ def to_s16(src, dst16=None):
     _check(lib.accflow_to_s16_f32(_p(src), sbs, ctypes.c_void_p(dst16.ptr()), dst16.bs, _p(_guard(src.device)), B, C, H * W,
                                   _stream()), "accflow_to_s16_f32")
     return dst16
-
-
-def _replay(cache, name):
-    """Re-issue a launch whose argument list a previous call with the same `cache` = (dict, key) stored (same tensors: the
-    refinement iterations); None when there is nothing to replay."""
-    if cache is None or profiler.ACTIVE is not None:
-        return None
-    hit = cache[0].get(cache[1])
-    if hit is None:
-        return None
-    _check(hit[0](*hit[1], _stream()), name + " (cached)")
-    return hit[2]
 
 
 def corr_lookup_s16(pyr, coords, out16, cache=None):
@@ -1395,16 +1327,10 @@ def corr_lookup_s16(pyr, coords, out16, cache=None):
     if (B, H8, W8) != (pyr.B, pyr.H8, pyr.W8) or tuple(out16.shape) != (B, LOOKUP_S16_CHANNELS, H8, W8):
         raise RuntimeError("corr_lookup_s16: shape mismatch")
     lv = pyr.levels
-    tm = profiler.ACTIVE
-    t0 = tm.begin() if tm is not None and tm.wants("corr_lookup") else None
     args = (_p(lv[0]), _p(lv[1]), _p(lv[2]), _p(lv[3]), _p(coords), ctypes.c_void_p(out16.ptr()), out16.bs,
             _p(_guard(coords.device)), B, H8, W8)
-    _check(lib.accflow_corr_lookup_disp_s16(*args, _stream()), "accflow_corr_lookup_disp_s16")
-    if t0 is not None:
-        tm.end("corr_lookup", t0, LOOKUP_BYTES_PER_PX * B * H8 * W8)
-    elif cache is not None and tm is None:
-        cache[0][cache[1]] = (lib.accflow_corr_lookup_disp_s16, args, out16, (pyr, coords))
-    return out16
+    return _launch(lib.accflow_corr_lookup_disp_s16, args, "accflow_corr_lookup_disp_s16",
+                   ("corr_lookup", lambda: (LOOKUP_BYTES_PER_PX * B * H8 * W8,)), cache, out16, (pyr, coords, out16))
 
 
 LOOKUP_FUSED_K = 336   # reduction length of the fused lookup -> convc1 kernel (10 x 32 + 16; accflow_corr_lookup_convc1_kpad)
@@ -1447,21 +1373,15 @@ def corr_lookup_convc1(pyr, coords, pk, out16=None, out=None, act=ACT_RELU, cach
         if tuple(out.shape) != (B, pk.Cout, H8, W8):
             raise RuntimeError("corr_lookup_convc1: out shape %s" % (tuple(out.shape),))
     lv = pyr.levels
-    tm = profiler.ACTIVE
-    t0 = tm.begin() if tm is not None and tm.wants("lookup_convc1") else None
     args = (_p(lv[0]), _p(lv[1]), _p(lv[2]), _p(lv[3]), _p(coords), _p(pk.wpatch16), _p(pk.wscale16),
             _p(pk.bias) if pk.bias is not None else None,
             ctypes.c_void_p(out16.ptr()) if out16 is not None else None, out16.bs if out16 is not None else 0,
             _p(out) if out is not None else None, out_bs, int(act), _p(_guard(coords.device)), B, H8, W8, pk.Cout)
-    _check(lib.accflow_corr_lookup_convc1_s16(*args, _stream()), "accflow_corr_lookup_convc1_s16")
-    ret = out16 if out16 is not None else out
-    if t0 is not None:
-        # work = the reference's convc1 flop (324 input channels); detail carries the lookup side's algorithmic bytes
-        tm.end("lookup_convc1", t0, 2.0 * 324 * pk.Cout * B * H8 * W8, "lookup+convc1 B%d %dx%d" % (B, H8, W8),
-               work_exec=2.0 * LOOKUP_FUSED_K * pk.Cout * B * H8 * W8)
-    elif cache is not None and tm is None:
-        cache[0][cache[1]] = (lib.accflow_corr_lookup_convc1_s16, args, ret, (pyr, coords, pk, out16, out))
-    return ret
+    # work = the reference's convc1 flop (324 input channels), executed: the fused pack's 336
+    return _launch(lib.accflow_corr_lookup_convc1_s16, args, "accflow_corr_lookup_convc1_s16",
+                   ("lookup_convc1", lambda: (2.0 * 324 * pk.Cout * B * H8 * W8, "lookup+convc1 B%d %dx%d" % (B, H8, W8),
+                                              2.0 * LOOKUP_FUSED_K * pk.Cout * B * H8 * W8)),
+                   cache, out16 if out16 is not None else out, (pyr, coords, pk, out16, out))
 
 
 def flow_from_coords_s16(coords1, dst0, dst1, stack16, motion16, motion_ch, is_flow=False, cache=None):
@@ -1481,9 +1401,8 @@ def flow_from_coords_s16(coords1, dst0, dst1, stack16, motion16, motion_ch, is_f
     args = (_p(coords1), _p(dst0), b0, _p(dst1), b1, ctypes.c_void_p(stack16.ptr()), stack16.bs,
             ctypes.c_void_p(motion16.ptr() if motion16 is not None else 0), motion16.bs if motion16 is not None else 0,
             int(motion_ch), _p(_guard(coords1.device)), int(bool(is_flow)), B, H8, W8)
-    _check(lib.accflow_flow_from_coords_s16(*args, _stream()), "accflow_flow_from_coords_s16")
-    if cache is not None and profiler.ACTIVE is None:
-        cache[0][cache[1]] = (lib.accflow_flow_from_coords_s16, args, True, (coords1, dst0, dst1, stack16, motion16))
+    _launch(lib.accflow_flow_from_coords_s16, args, "accflow_flow_from_coords_s16", None, cache, True,
+            (coords1, dst0, dst1, stack16, motion16))
 
 
 def _corr_lookup_rowmajor(pyramid, coords, out=None):
@@ -1495,14 +1414,10 @@ def _corr_lookup_rowmajor(pyramid, coords, out=None):
     out_bs = _plane4(out, "out")
     for t in pyramid:
         _dense(t, "pyramid level")
-    tm = profiler.ACTIVE
-    t0 = tm.begin() if tm is not None and tm.wants("corr_lookup") else None
-    _check(lib.accflow_corr_lookup_f32(_p(pyramid[0]), _p(pyramid[1]), _p(pyramid[2]), _p(pyramid[3]),
-                                       _p(coords), _p(out), out_bs, B, H8, W8, _stream()),
-           "accflow_corr_lookup_f32")
-    if t0 is not None:  # algorithmic bytes: 4 levels x 10x10 fp32 window + 8 B coords + 324 fp32 written per px
-        tm.end("corr_lookup", t0, LOOKUP_BYTES_PER_PX * B * H8 * W8)
-    return out
+    # algorithmic bytes: 4 levels x 10x10 fp32 window + 8 B coords + 324 fp32 written per px
+    return _launch(lib.accflow_corr_lookup_f32, (_p(pyramid[0]), _p(pyramid[1]), _p(pyramid[2]), _p(pyramid[3]), _p(coords),
+                                                 _p(out), out_bs, B, H8, W8),
+                   "accflow_corr_lookup_f32", ("corr_lookup", lambda: (LOOKUP_BYTES_PER_PX * B * H8 * W8,)), ret=out)
 
 
 def convex_upsample(flow, mask, out=None):

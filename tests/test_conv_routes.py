@@ -7,8 +7,8 @@ of its own), each with the real `ops` call, the plan it must get and a gate.
 
   CPU (no GPU needed)
     test_row_plans_as_stated      the row's descriptor, filled with dummy pointers by plan_descriptor() - which restates
-                                  PackedConv's pack rules and the workspace rule of ops._conv2d / _conv2d_s16 / conv2d_multi /
-                                  conv2d_tapgemm - plans to the row's key;
+                                  PackedConv's pack rules and the workspace rule of the four forms of ops._conv_desc - plans
+                                  to the row's key;
     test_table_is_complete        the launch lines of the direct kernel, the `case` labels of the im2col and fp32-MFMA
                                   launchers and the multi-source launch lines, counted in the sources: each has a row or is a
                                   named switch-only entry (SWITCH_ONLY);
@@ -390,7 +390,7 @@ def plan_descriptor(row):
     d.epi = {"store": 0, "res_relu": 1, "gru_zr": 2, "gru_q": 3, "accum": 4}[row.epi]
     d.act = {"store": 0, "res_relu": 1, "gru_zr": 2, "gru_q": 3, "accum": 0}[row.epi]
     d.wsplit = DUMMY if has_split else None
-    if row.s16 or row.out16:       # ops._conv2d_s16
+    if row.s16 or row.out16:       # ops._FORM_S16
         assert f16 and has_patch
         d.wpatch = d.wpatch16 = d.wscale16 = DUMMY
         d.wsplit16 = DUMMY if has_split16 else None

@@ -113,7 +113,7 @@ def test_c_abi_rejects_bad_tapgemm_descriptors(ops):
         x16 = ops.S16.from_float(dev(torch.randn(B, 128, H, W)))
         cache = {}
         ops.conv2d_tapgemm(p1, p2, x16, cache=(cache, "k"))
-        d = cache["k"][0]
+        d = cache["k"][3][0]        # (fn, args, ret, keep): the kept descriptor leads the keep-alive tuple
         st = torch.cuda.current_stream().cuda_stream
         assert lib.accflow_conv2d_f32(ctypes.byref(d), st) == 0
         for field, bad in (("tg_rows", 19), ("tg_rows", 0), ("tg_coutpad", 16), ("act", ops.ACT_NONE), ("tg_out", None),
