@@ -705,4 +705,5 @@ int accflow_direct_launch_s16k(const accflow_conv_desc& d, int kt, dim3 grid, hi
 int accflow_direct_launch_f16(const accflow_conv_desc& d, int tc, bool w4, dim3 grid, hipStream_t st);
 int accflow_direct_launch_f16_norm(const accflow_conv_desc& d, int tc, bool kt9, dim3 grid, hipStream_t st);   // kt9: the 9-tap loop (128-channel kernel)
 int accflow_direct_launch_bf16(const accflow_conv_desc& d, int tc, int nt, bool w4, dim3 grid, hipStream_t st);
+int accflow_direct_launch_bf16x3(const accflow_conv_desc& d, int tc, bool w4, dim3 grid, hipStream_t st);   // nt == 2, its own unit
 int accflow_direct_launch_bf16_norm(const accflow_conv_desc& d, int tc, int nt, dim3 grid, hipStream_t st);

@@ -2,13 +2,6 @@
 // groups: this unit and conv2d_f32_v1 / _v2 / _v3.hip).
 #include "conv2d_f32_kernel.h"
 
-int accflow_launch_conv_f32_1412(const accflow_conv_desc& d, hipStream_t st);
-int accflow_launch_conv_f32_1411(const accflow_conv_desc& d, hipStream_t st);
-int accflow_launch_conv_f32_2212(const accflow_conv_desc& d, hipStream_t st);
-int accflow_launch_conv_f32_2211(const accflow_conv_desc& d, hipStream_t st);
-int accflow_launch_conv_f32_1431(const accflow_conv_desc& d, hipStream_t st);
-int accflow_launch_conv_f32_2221(const accflow_conv_desc& d, hipStream_t st);
-
 int accflow_launch_conv_f32(const accflow_conv_desc& d, int wc, int wp, int tc, int tp, hipStream_t st) {
   const int key = wc * 1000 + wp * 100 + tc * 10 + tp;
   switch (key) {

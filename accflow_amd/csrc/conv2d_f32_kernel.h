@@ -178,3 +178,11 @@ int launch_conv(const accflow_conv_desc& d, hipStream_t st) {
 
 }  // namespace
 
+// launch_conv<WC, WP, TC, TP> of the instantiation groups conv2d_f32_v1 / _v2 / _v3.hip (conv2d_f32.hip dispatches over them)
+int accflow_launch_conv_f32_1412(const accflow_conv_desc& d, hipStream_t st);
+int accflow_launch_conv_f32_1411(const accflow_conv_desc& d, hipStream_t st);
+int accflow_launch_conv_f32_2212(const accflow_conv_desc& d, hipStream_t st);
+int accflow_launch_conv_f32_2211(const accflow_conv_desc& d, hipStream_t st);
+int accflow_launch_conv_f32_1431(const accflow_conv_desc& d, hipStream_t st);
+int accflow_launch_conv_f32_2221(const accflow_conv_desc& d, hipStream_t st);
+

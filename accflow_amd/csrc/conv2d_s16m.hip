@@ -1,6 +1,7 @@
 // Host side of the multi-source S16 convolution kernel (conv_s16m_kernel.h): the launch of a plan (validation, wave-layout
 // choice and split-K: conv_plan.cpp) and its weight pack (accflow_conv_pack_multi16).
 #include "conv_s16m_kernel.h"
+#include "pack_terms.h"
 
 namespace {
 
@@ -11,33 +12,18 @@ struct multi_pack_args {
 };
 
 // wscale16[ch] = 2^-(k + ACCFLOW_F16_ASHIFT), k such that the row's largest |w * scale| over ALL sources * 2^k lies in
-// [2^10, 2^11) (conv_row_scale16_kernel's rule, conv2d.hip): one workgroup per output channel
+// [2^10, 2^11) (the packs' one row-scale rule, pack_terms.h): one workgroup per output channel
 __global__ __launch_bounds__(256) void conv_row_scale_multi_kernel(const multi_pack_args a, const float* __restrict__ scale, int Cout,
                                                                    float* __restrict__ wscale16) {
-  __shared__ float red[256];
   const int ch = blockIdx.x;
   float m = 0.0f;
   if (ch < Cout)
     for (int s = 0; s < a.nsrc; ++s)
       for (int j = threadIdx.x; j < a.rowlen[s]; j += 256) m = fmaxf(m, fabsf(a.w[s][(long long)ch * a.rowlen[s] + j]));
-  red[threadIdx.x] = m;
-  __syncthreads();
-  for (int s = 128; s > 0; s >>= 1) {
-    if (threadIdx.x < s) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
-    __syncthreads();
-  }
+  m = pack_block_max256(m);
   if (threadIdx.x) return;
-  m = red[0];
   if (ch < Cout && scale) m *= fabsf(scale[ch]);
-  int k = 0;
-  if (m > 0.0f && m < 3.0e38f) {
-    int e;
-    frexpf(m, &e);
-    k = 11 - e;
-    if (k > 100) k = 100;
-    if (k < -100) k = -100;
-  }
-  wscale16[ch] = ldexpf(1.0f, -(k + ACCFLOW_F16_ASHIFT));
+  wscale16[ch] = pack_row_scale16(m);
 }
 
 // one source's steps [step0, step0 + ceil(C/16) * T) of the pack [term][step][2 octets][CoutPad][8]
@@ -59,14 +45,8 @@ __global__ __launch_bounds__(256) void conv_pack_multi16_kernel(const float* __r
     val = w[((long long)ch * C + c) * T + tap];
     if (scale) val *= scale[ch];
   }
-  float rr = val * (ldexpf(1.0f, -ACCFLOW_F16_ASHIFT) / wscale16[ch]);
   const long long dst = step0 * 2 * CoutPad * 8 + idx;
-#pragma unroll
-  for (int t = 0; t < 3; ++t) {
-    const _Float16 hq = t < 2 ? (_Float16)rr : (_Float16)0.0f;
-    wp[t * per_term + dst] = __builtin_bit_cast(unsigned short, hq);
-    rr -= (float)hq;
-  }
+  pack_store_f16x2z(wp + dst, per_term, val * pack_row_mul16(wscale16[ch]));
 }
 
 long long multi_steps(int nsrc, const int* C, const int* KH, const int* KW) {

@@ -1,23 +1,13 @@
-// Device code shared by the convolution translation units (conv2d.hip: C-ABI, packing, small-Cout kernels;
-// conv2d_f32.hip: fp32-MFMA im2col kernel; conv2d_bf16s.hip: split-bf16 im2col kernel + displaced correlation store;
-// conv2d_direct.hip: split-bf16 direct-A patch kernel).  Everything here is internal linkage.  The dispatch itself is host
-// code without a HIP header: conv_plan.h / conv_plan.cpp, on the tile constants of conv_tiles.h.
+// Device code shared by the convolution translation units (conv_small.hip: the <= 4-output-channel kernels; conv_pack.hip:
+// the weight / operand packs; conv2d_f32.hip: fp32-MFMA im2col kernel; conv2d_bf16s.hip: split-bf16 im2col kernel +
+// displaced correlation store; conv2d_direct.hip: split-bf16 direct-A patch kernel).  Everything here is internal linkage.
+// The dispatch itself is host code without a HIP header: conv_plan.h / conv_plan.cpp, on the tile constants of
+// conv_tiles.h; conv2d.hip runs it and calls the launchers of launchers.h.
 #pragma once
 #include "common.h"
 #include <stdlib.h>
-#include "conv_plan.h"
+#include "launchers.h"
 
-// Dispatch: conv_plan.cpp turns a validated descriptor into a conv_plan (kernel family, tile, loop variant, split-K parts,
-// statistic slots); the launchers below execute a plan - they keep the grid arithmetic and the choice of the instantiation.
-// launch entry points of the kernel families (one translation unit each, so that they compile in parallel)
-int accflow_launch_conv_f32(const accflow_conv_desc& d, int wc, int wp, int tc, int tp, hipStream_t st);
-int accflow_launch_conv_bf16s(const accflow_conv_desc& d, int tc, int tp, int Z, hipStream_t st);
-int conv_ksplit_reduce_launch(const accflow_conv_desc& d, int Z, hipStream_t st);  // conv2d_direct.hip
-int accflow_launch_corr_disp_bf16s(const accflow_conv_desc& d, hipStream_t st);
-int accflow_launch_corr_disp_direct(const accflow_conv_desc& d, hipStream_t st);
-int accflow_launch_conv_direct(const accflow_conv_desc& d, const conv_plan& p, hipStream_t st);
-int accflow_launch_conv_s16m(const accflow_conv_desc& d, const conv_plan& p, hipStream_t st);   // multi-source S16 kernel (conv2d_s16m.hip)
-int accflow_launch_conv_stem(const accflow_conv_desc& d, hipStream_t st);                        // conv_stem.hip
 #ifndef ACCFLOW_EPI_GRU_AHEAD
 #define ACCFLOW_EPI_GRU_AHEAD 3     // (1 = round 1-5 behaviour; 4 spills 5 registers and costs 6 % conv rate: profiles/r06_ab_gru_epilogue_prefetch.txt)
 #endif

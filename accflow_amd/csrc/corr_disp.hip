@@ -17,11 +17,12 @@
 // in memory (neighbouring dx are 512 B apart, a whole level of one block is <= 3.9 MB), so the GEMM's tile stores,
 // the pooling passes and the window reads all stay inside a few DRAM pages instead of striding by 4*P bytes.
 //
-// Level 0 is written in this layout straight from the matrix-core GEMM (conv2d.hip, corr_disp_store: the
+// Level 0 is written in this layout straight from the matrix-core GEMM (conv_common.h, corr_disp_store: the
 // 128x128 accumulator tile is sheared through LDS so that stores run along p); levels 1..3 are pooled in
 // displacement space with F.avg_pool2d(2, 2) semantics (floor sizes, ((a+b)+c)+d then * 0.25, pool of pool).
 // The lookup math is corr_lookup.hip's (CorrBlock.__call__, raft/corr.py:24-45 + bilinear_sampler).
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 

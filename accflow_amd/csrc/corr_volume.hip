@@ -5,7 +5,10 @@
 // the LDS layout the 32x32x2 fragments want, so the global->LDS staging is plain coalesced float4 rows
 // and the store is coalesced along j.  Levels 1..3 are produced by one streaming kernel per query
 // plane that pools hierarchically through LDS with the reference's pool-of-pool rounding order.
+// The split modes run level 0 as a 1x1 convolution on the matrix-core kernels (accflow_corr_level0_bf16s and the per-frame
+// packs below): the host side builds the descriptors, conv_pack.hip packs the feature maps.
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 
@@ -162,13 +165,63 @@ int accflow_gemm_atb_f32(const float* A, const float* Bm, float* C, int M, int N
   ACCFLOW_RETURN_LAUNCH_STATUS();
 }
 
+// All-pairs correlation as B independent 1x1 "convolutions" on the split-bf16 matrix cores: for pair b the
+// K-major feature map fmap1[b] (C x P) plays the weights (C -> P output "channels"), fmap2[b] the input, so
+// out[i][j] = <f1[:, i], f2[:, j]> / sqrt(C) lands directly in the (P x P) level-0 layout.  ws: Kpad*CoutPad*3
+// uint16 + Kpad*4 int32 of workspace, reused pair after pair on the same stream.
+// disp != 0: level 0 in the displacement-indexed layout of corr_disp.hip instead.
+// guard: device flag of the f16x3 mode (caller-owned, may be NULL).
+// lvl1 (displaced layout only): the register-only GEMM also emits level 1; *lvl1_done tells the caller so.
 int accflow_corr_level0_bf16s(const float* fmap1, const float* fmap2, float* lvl0, void* ws, int B, int C, int H8,
-                              int W8, int mode, int disp, int* guard, hipStream_t st, float* lvl1, int* lvl1_done);
-extern "C" int accflow_corr_disp_supported(int H8, int W8);
-extern "C" int accflow_corr_disp_pool_f32(const float* lvl0, float* lvl1, float* lvl2, float* lvl3, int B, int H8,
-                                          int W8, void* stream);
-int accflow_corr_disp_pool_from(const float* lvl0, float* lvl1, float* lvl2, float* lvl3, int B, int H8, int W8, int first,
-                                hipStream_t st);
+                              int W8, int mode, int disp, int* guard, hipStream_t st, float* lvl1, int* lvl1_done) {
+  if (lvl1_done) *lvl1_done = 0;
+  const int P = H8 * W8;
+  const int Kpad = accflow_conv_kpad(C, 1, 1), CoutPad = accflow_conv_coutpad(P);
+  unsigned short* wsplit = reinterpret_cast<unsigned short*>(ws);
+  int* ktab = reinterpret_cast<int*>(wsplit + 3LL * Kpad * CoutPad);
+  const float cscale = 1.0f / sqrtf((float)C);
+  // the displaced layout comes out of the direct kernel (a 1x1 convolution's [term][step][octet][ch][8] weight pack
+  // is the [term][k/8][ch][8] split itself); in f16x3 mode fmap1 is packed as fp16 hi + lo
+  const bool direct = disp && C >= 16 && C % 16 == 0 && W8 % 2 == 0 && lvl1;
+  const bool f16 = direct && mode == ACCFLOW_CONV_F16X3;
+  if (mode == ACCFLOW_CONV_F16X3 && !f16) mode = ACCFLOW_CONV_BF16X6;
+  // f16x3: both feature maps are split as fp16 hi + lo of x * 2^ACCFLOW_F16_ASHIFT (exact scaling; keeps lo a normal
+  // number down to |x| = 2^-7) and the accumulator is multiplied by 2^-2*ASHIFT in the store
+  const float fs = f16 ? ldexpf(1.0f, ACCFLOW_F16_ASHIFT) : 1.0f;
+  for (int b = 0; b < B; ++b) {
+    accflow_pack_kmajor(fmap1 + (long long)b * C * P, P, C, Kpad, CoutPad, wsplit, cscale * fs, f16 ? 1 : 0, guard, st);
+    if (b == 0) accflow_pack_ktab_1x1(C, Kpad, ktab, st);
+    accflow_conv_desc d = {};
+    d.in0 = fmap2 + (long long)b * C * P; d.in0_bs = (long long)C * P; d.C0 = C; d.C1 = 0;
+    d.B = 1; d.H = H8; d.W = W8; d.OH = H8; d.OW = W8; d.KH = 1; d.KW = 1; d.stride = 1; d.padH = 0; d.padW = 0;
+    d.Cout = P; d.wpack = reinterpret_cast<const float*>(wsplit) /* unused in split modes */; d.ktab = ktab;
+    const long long pair_elems = disp ? (long long)((P + 127) / 128) * 128 * P : (long long)P * P;  // displaced: p padded to 128
+    d.Kpad = Kpad; d.CoutPad = CoutPad; d.out = lvl0 + (long long)b * pair_elems; d.out_bs = pair_elems;
+    d.act = ACCFLOW_ACT_NONE; d.epi = ACCFLOW_EPI_STORE; d.wsplit = wsplit; d.mode = mode;
+    if (direct) {  // register-only GEMM: fmap2 packed the same way (no scale) right behind the k-table
+      unsigned short* bsplit = reinterpret_cast<unsigned short*>(reinterpret_cast<char*>(ws) + 3LL * Kpad * CoutPad * 2 +
+                                                                 (long long)Kpad * 16);
+      accflow_pack_kmajor(fmap2 + (long long)b * C * P, P, C, Kpad, CoutPad, bsplit, fs, f16 ? 1 : 0, guard, st);
+      d.in0 = reinterpret_cast<const float*>(bsplit);
+      d.wpatch = wsplit;
+      if (f16) { d.wpatch16 = wsplit; d.guard = guard; d.acc_scale = 1.0f / (fs * fs); }
+      if (!lvl1) return 1;
+      d.out2 = lvl1 + (long long)b * ((P + 127) / 128) * 128 * (H8 >> 1) * (W8 >> 1);
+      const int rc = accflow_launch_corr_disp_direct(d, st);
+      if (rc) return rc;
+      if (lvl1_done) *lvl1_done = 1;
+      continue;
+    }
+    if (disp) {
+      const int rc = accflow_launch_corr_disp_bf16s(d, st);
+      if (rc) return rc;
+      continue;
+    }
+    const int rc = accflow_conv2d_f32(&d, st);
+    if (rc) return rc;
+  }
+  return (int)hipGetLastError();
+}
 
 static int corr_volume_impl(const float* fmap1, const float* fmap2, float* lvl0, float* lvl1, float* lvl2, float* lvl3,
                             void* ws, int mode, int B, int C, int H8, int W8, void* stream) {
@@ -225,4 +278,58 @@ extern "C" int accflow_corr_volume_disp_f32(const float* fmap1, const float* fma
   if (rc) return rc;
   // the register-only GEMM wrote level 1 with level 0 (bit-identical to pooling level 0): pool from level 1 on
   return accflow_corr_disp_pool_from(lvl0, lvl1, lvl2, lvl3, B, H8, W8, lvl1_done ? 1 : 0, as_stream(stream));
+}
+
+// Per-FRAME operand packs of the displaced correlation GEMM.  A 7-frame sequence evaluates 11 pairs over 7 feature maps
+// (frame 0 is the target of 6 of them): packing per pair split every map up to 6 times and needed the pair-major copies
+// torch.cat made of them.  One pack per frame, x * 2^ACCFLOW_F16_ASHIFT as fp16 hi + lo (or 3 bf16 terms), serves as
+// A (queries) and as B (targets); the 1/sqrt(C) of corr.py:55 moves into the accumulator scale.
+extern "C" long long accflow_corr_pack_bytes(int C, int H8, int W8) {
+  return 3LL * accflow_conv_kpad(C, 1, 1) * accflow_conv_coutpad(H8 * W8) * 2;
+}
+
+extern "C" int accflow_corr_pack_f32(const float* fmaps, void* packs, int mode, int* guard, int F, int C, int H8, int W8,
+                                     void* stream) {
+  if (!fmaps || !packs || F <= 0 || C < 16 || (C % 16) || (W8 & 1) || !accflow_corr_disp_supported(H8, W8)) return 1;
+  if (mode != ACCFLOW_CONV_BF16X3 && mode != ACCFLOW_CONV_BF16X6 && mode != ACCFLOW_CONV_F16X3) return 1;
+  const int P = H8 * W8, Kpad = accflow_conv_kpad(C, 1, 1), CoutPad = accflow_conv_coutpad(P);
+  const bool f16 = mode == ACCFLOW_CONV_F16X3;
+  const float fs = f16 ? ldexpf(1.0f, ACCFLOW_F16_ASHIFT) : 1.0f;
+  const long long bytes = accflow_corr_pack_bytes(C, H8, W8);
+  for (int f = 0; f < F; ++f)
+    accflow_pack_kmajor(fmaps + (long long)f * C * P, P, C, Kpad, CoutPad, reinterpret_cast<char*>(packs) + f * bytes, fs,
+                        f16 ? 1 : 0, guard, as_stream(stream));
+  ACCFLOW_RETURN_LAUNCH_STATUS();
+}
+
+extern "C" int accflow_corr_volume_disp_packed_f32(const void* packs, int F, const int* idx1, const int* idx2, float* lvl0,
+                                                   float* lvl1, float* lvl2, float* lvl3, int mode, int* guard, int B,
+                                                   int C, int H8, int W8, void* stream) {
+  if (!packs || F <= 0 || !idx1 || !idx2 || !lvl0 || !lvl1 || !lvl2 || !lvl3 || B <= 0 || C < 16 || (C % 16) || (W8 & 1) ||
+      !accflow_corr_disp_supported(H8, W8))
+    return 1;
+  for (int b = 0; b < B; ++b)   // (host arrays) every pair inside the pack buffer, checked before the first launch
+    if (idx1[b] < 0 || idx2[b] < 0 || idx1[b] >= F || idx2[b] >= F) return 1;
+  if (mode != ACCFLOW_CONV_BF16X3 && mode != ACCFLOW_CONV_BF16X6 && mode != ACCFLOW_CONV_F16X3) return 1;
+  hipStream_t st = as_stream(stream);
+  const int P = H8 * W8, Kpad = accflow_conv_kpad(C, 1, 1), CoutPad = accflow_conv_coutpad(P);
+  const bool f16 = mode == ACCFLOW_CONV_F16X3;
+  const float fs = f16 ? ldexpf(1.0f, ACCFLOW_F16_ASHIFT) : 1.0f;
+  const long long bytes = accflow_corr_pack_bytes(C, H8, W8);
+  const long long pair0 = (long long)((P + 127) / 128) * 128 * P, pair1 = (long long)((P + 127) / 128) * 128 * (H8 >> 1) * (W8 >> 1);
+  for (int b = 0; b < B; ++b) {
+    const char* a = reinterpret_cast<const char*>(packs) + idx1[b] * bytes;
+    const char* t = reinterpret_cast<const char*>(packs) + idx2[b] * bytes;
+    accflow_conv_desc d = {};
+    d.in0 = reinterpret_cast<const float*>(t);
+    d.C0 = C; d.B = 1; d.H = H8; d.W = W8; d.OH = H8; d.OW = W8; d.KH = 1; d.KW = 1; d.stride = 1;
+    d.Cout = P; d.Kpad = Kpad; d.CoutPad = CoutPad;
+    d.out = lvl0 + b * pair0; d.out_bs = pair0; d.out2 = lvl1 + b * pair1;
+    d.mode = mode; d.wpatch = a;
+    if (f16) { d.wpatch16 = a; d.guard = guard; }
+    d.acc_scale = (1.0f / sqrtf((float)C)) / (fs * fs);   // corr / sqrt(dim) (corr.py:55) and the operands' 2^ASHIFT
+    const int rc = accflow_launch_corr_disp_direct(d, st);
+    if (rc) return rc;
+  }
+  return accflow_corr_disp_pool_from(lvl0, lvl1, lvl2, lvl3, B, H8, W8, 1, st);
 }

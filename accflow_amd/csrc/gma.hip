@@ -1,10 +1,10 @@
 // GMA attention (gma/modules.py:54-76, content-only branch, heads = 1) and aggregation
 // (gma/modules.py:102-115).  The P x P attention matrix is materialised once per image1 (fp32, as the
 // reference does) and re-read every GRU iteration by the aggregation GEMM, which is the HBM-bound part.
+// The matrix-core routes are 1x1 convolutions built here: v * gamma (q, k) packed per call (conv_pack.hip), the descriptor
+// planned and launched on the direct or the im2col kernel.
 #include "common.h"
-
-int accflow_gemm_atb_f32(const float* A, const float* Bm, float* C, int M, int N, int K, long long a_bs,
-                         long long b_bs, long long c_bs, int batch, float scale, hipStream_t st);
+#include "launchers.h"
 
 namespace {
 
@@ -173,14 +173,8 @@ __global__ __launch_bounds__(1024) void col_softmax16_kernel(float* __restrict__
 
 }  // namespace
 
-int accflow_gma_aggregate_conv(const float* attnT, const float* v, const float* fmap, const float* gamma, float* out,
-                               long long out_bs, void* ws, int mode, int* guard, int B, int D, int H, int W, hipStream_t st);
-
 // Transposed-attention pair used by the estimator's hot path (same numbers, j-major storage):
 //   attnT[b][j][i] = softmax_j(scale * <q_i, k_j>)
-int accflow_corr_level0_bf16s(const float* fmap1, const float* fmap2, float* lvl0, void* ws, int B, int C, int H8,
-                              int W8, int mode, int disp, int* guard, hipStream_t st, float* lvl1, int* lvl1_done);
-
 extern "C" long long accflow_gma_attention_ws_bytes(int D, int H, int W) { return accflow_corr_volume_ws_bytes(D, H, W); }
 
 extern "C" int accflow_gma_attention_t_f32(const float* qk, float* attnT, void* ws, int mode, int B, int D, int H, int W,
@@ -218,29 +212,163 @@ extern "C" long long accflow_gma_aggregate_ws_bytes(int B, int D, int P) {
   return a > b ? a : b;
 }
 
+// GMA aggregation (gma/modules.py:102-115) as B independent 1x1 convolutions on the split-bf16 matrix cores:
+// out[b][d][i] = fmap[b][d][i] + gamma * sum_j v[b][d][j] * attnT[b][j][i].  The TRANSPOSED attention (j-major) is
+// exactly a (1, P channels, h, w) activation tensor, v[b] the (D x P) weight matrix (re-split every call, gamma folded
+// in), and the residual add is the conv's accumulate epilogue.  ws as accflow_corr_volume_ws_bytes-style scratch:
+// 3*Kpad*CoutPad uint16 + Kpad int4.
+static int gma_aggregate_conv(const float* attnT, const float* v, const float* fmap, const float* gamma, float* out,
+                              long long out_bs, void* ws, int mode, int* guard, int B, int D, int H, int W, hipStream_t st) {
+  const int P = H * W;
+  const int Kpad = accflow_conv_kpad(P, 1, 1), CoutPad = accflow_conv_coutpad(D);
+  if (mode == ACCFLOW_CONV_F16X3 && B == 1 && P >= 16) {
+    // one item (or a stacked run of items that share the attention): the LDS-patch kernel (about twice the im2col
+    // kernel's rate) with v * gamma packed as its fp16 weights; split-K fills the chip (115 pixel tiles at 720x1280)
+    unsigned short* wpatch16 = reinterpret_cast<unsigned short*>(ws);
+    float* wscale16 = reinterpret_cast<float*>(wpatch16 + accflow_conv_patch_elems(D, P, 1, 1));
+    float* kws = wscale16 + CoutPad;
+    accflow_pack_row_scale16(v, nullptr, D, P, CoutPad, 1, wscale16, gamma, st);
+    accflow_pack_patch(v, nullptr, D, P, 1, CoutPad, wpatch16, 1, wscale16, 2, gamma, st);
+    accflow_conv_desc d = {};
+    d.in0 = attnT; d.in0_bs = (long long)P * P; d.C0 = P;
+    d.B = 1; d.H = H; d.W = W; d.OH = H; d.OW = W; d.KH = 1; d.KW = 1; d.stride = 1;
+    d.Cout = D; d.Kpad = Kpad; d.CoutPad = CoutPad;
+    d.out = out; d.out_bs = out_bs;
+    d.act = ACCFLOW_ACT_NONE; d.epi = ACCFLOW_EPI_ACCUM; d.e0 = fmap; d.e0_bs = (long long)D * P;
+    d.wpatch = wpatch16; d.wpatch16 = wpatch16; d.wscale16 = wscale16; d.mode = mode; d.guard = guard;
+    d.kws = kws; d.kws_elems = 8LL * D * P;
+    conv_plan p;
+    if (conv_plan_direct(d, D > 64 ? 2 : 1, false, p)) return 1;
+    return accflow_launch_conv_direct(d, p, st);
+  }
+  // the im2col route packs v as split terms only: accflow_conv2d_f32 would hand <= 32 rows to the fp32 kernels, which read
+  // the pack as fp32 (the estimator's D is 128)
+  if (D <= 32) return 1;
+  unsigned short* wsplit = reinterpret_cast<unsigned short*>(ws);
+  int* ktab = reinterpret_cast<int*>(wsplit + 3LL * Kpad * CoutPad * B);
+  float* wscale16 = reinterpret_cast<float*>(reinterpret_cast<char*>(ktab) + (long long)Kpad * 16);  // [B][CoutPad]
+  float* kws = wscale16 + (((long long)B * CoutPad + 3) & ~3LL);   // B == 1: 8 * D * P floats of split-K partials
+  accflow_pack_ktab_1x1(P, Kpad, ktab, st);
+  // f16x3: v[b] * gamma as fp16 hi + lo with per-row (and per-pair) power-of-two scales; the attention (values in
+  // [0, 1]) is split by the kernel with the usual 2^ACCFLOW_F16_ASHIFT.  Half the MFMAs of the bf16x6 form.
+  const bool f16 = mode == ACCFLOW_CONV_F16X3 && (P % 64) == 0;
+  if (mode == ACCFLOW_CONV_F16X3 && !f16) mode = ACCFLOW_CONV_BF16X6;
+  if (f16) accflow_pack_row_scale16(v, nullptr, D, P, CoutPad, B, wscale16, gamma, st);
+  accflow_pack_bf16s(v, nullptr, D, P, 1, 1, Kpad, CoutPad, B, wsplit, 0, 1.0f, gamma, f16 ? wscale16 : nullptr, st);
+  accflow_conv_desc d = {};
+  d.in0 = attnT; d.in0_bs = (long long)P * P; d.C0 = P; d.C1 = 0;
+  d.B = B; d.H = H; d.W = W; d.OH = H; d.OW = W; d.KH = 1; d.KW = 1; d.stride = 1;
+  d.Cout = D; d.wpack = reinterpret_cast<const float*>(wsplit); d.ktab = ktab; d.Kpad = Kpad; d.CoutPad = CoutPad;
+  d.out = out; d.out_bs = out_bs;
+  d.act = ACCFLOW_ACT_NONE; d.epi = ACCFLOW_EPI_ACCUM; d.e0 = fmap; d.e0_bs = (long long)D * P;
+  d.wsplit = wsplit; d.wsplit_bs = 3LL * Kpad * CoutPad * 2; d.mode = mode;
+  if (f16) { d.wsplit16 = wsplit; d.wscale16 = wscale16; d.guard = guard; }
+  if (B == 1) { d.kws = kws; d.kws_elems = 8LL * D * P; }
+  if (P % 64 == 0) {  // 64-pixel tiles never straddle two pairs: as few launches as 32-bit buffer offsets allow
+    const long long per_pair = (long long)P * P * 4;
+    const int chunk = (int)(((1LL << 32) - 1) / per_pair);
+    if (chunk < 1) return 1;
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+      accflow_conv_desc e = d;
+      e.B = B - b0 < chunk ? B - b0 : chunk;
+      e.in0 = attnT + (long long)b0 * P * P; e.out = out + (long long)b0 * out_bs; e.e0 = fmap + (long long)b0 * D * P;
+      e.wsplit = wsplit + 3LL * Kpad * CoutPad * b0;
+      if (f16) { e.wsplit16 = e.wsplit; e.wscale16 = wscale16 + (long long)b0 * CoutPad; }
+      const int rc = accflow_conv2d_f32(&e, st);
+      if (rc) return rc;
+    }
+    return 0;
+  }
+  for (int b = 0; b < B; ++b) {                           // ragged sizes: one launch per pair
+    accflow_conv_desc e = d;
+    e.B = 1; e.in0 = attnT + (long long)b * P * P; e.out = out + (long long)b * out_bs; e.e0 = fmap + (long long)b * D * P;
+    e.wsplit = wsplit + 3LL * Kpad * CoutPad * b; e.wsplit_bs = 0;
+    const int rc = accflow_conv2d_f32(&e, st);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
 extern "C" int accflow_gma_aggregate_t_f32(const float* attnT, const float* v, const float* fmap, const float* gamma,
                                            float* out, long long out_bs, void* ws, int mode, int* guard, int B, int D,
                                            int H, int W, void* stream) {
   if (!attnT || !v || !fmap || !gamma || !out || !ws || B <= 0 || D <= 0 || H <= 0 || W <= 0) return 1;
   if (mode == ACCFLOW_CONV_F32) return 1;  // the fp32 path is accflow_gma_aggregate_f32 on the i-major attention
-  return accflow_gma_aggregate_conv(attnT, v, fmap, gamma, out, out_bs, ws, mode, guard, B, D, H, W, as_stream(stream));
+  return gma_aggregate_conv(attnT, v, fmap, gamma, out, out_bs, ws, mode, guard, B, D, H, W, as_stream(stream));
 }
-
-int accflow_gma_aggregate_s16_impl(const void* attn16, const float* v, const float* fmap, long long fmap_bs, const float* gamma,
-                                   float* out, long long out_bs, void* out16, long long out16_bs, void* ws, int* guard, int n,
-                                   int D, int H, int W, hipStream_t st);
 
 extern "C" long long accflow_gma_aggregate_s16_ws_bytes(int n, int D, int P) {
   const long long CoutPad = ((long long)n * D + 127) / 128 * 128;
   return accflow_conv_patch_elems(n * D, P, 1, 1) * 2 + CoutPad * 4 + 8LL * n * D * P * 4;
 }
 
+// GMA aggregation on the pre-split attention (accflow_gma_attention_s16): ONE GEMM for the n batch items that share an
+// attention matrix - rows = the n x D channels of v * gamma (packed per call as fp16 weights with their row scales), the
+// S16 attention as the activation operand through the direct kernel's DMA loader (no split in the K loop: the matrix is
+// constant over the refinement iterations), split-K over the P = h*w deep reduction - whose epilogue reads each item's
+// residual and writes each item's slice (fp32 and / or S16) through the channel-block scatter: no copies around it.
+static int gma_aggregate_s16_impl(const void* attn16, const float* v, const float* fmap, long long fmap_bs, const float* gamma,
+                                  float* out, long long out_bs, void* out16, long long out16_bs, void* ws, int* guard, int n,
+                                  int D, int H, int W, hipStream_t st) {
+  const int P = H * W, Cout = n * D;
+  const int Kpad = accflow_conv_kpad(P, 1, 1), CoutPad = accflow_conv_coutpad(Cout);
+  unsigned short* wpatch16 = reinterpret_cast<unsigned short*>(ws);
+  float* wscale16 = reinterpret_cast<float*>(wpatch16 + accflow_conv_patch_elems(Cout, P, 1, 1));
+  float* kws = wscale16 + CoutPad;
+  accflow_pack_rows16(v, Cout, P, CoutPad, wpatch16, wscale16, gamma, st);
+  accflow_conv_desc d = {};
+  d.in0 = reinterpret_cast<const float*>(attn16); d.in0_bs = accflow_s16_item_words(P, H, W); d.C0 = P; d.in_fmt = 1;
+  d.B = 1; d.H = H; d.W = W; d.OH = H; d.OW = W; d.KH = 1; d.KW = 1; d.stride = 1;
+  d.Cout = Cout; d.Kpad = Kpad; d.CoutPad = CoutPad;
+  d.out = out; d.out_bs = (long long)n * out_bs;
+  d.out16 = out16; d.out16_bs = (long long)n * out16_bs;
+  d.act = ACCFLOW_ACT_NONE; d.epi = ACCFLOW_EPI_ACCUM; d.e0 = fmap; d.e0_bs = (long long)n * fmap_bs;
+  d.cb = D; d.out_cbs = out_bs; d.e0_cbs = fmap_bs; d.out16_cbs = out16_bs;
+  d.wpatch = wpatch16; d.wpatch16 = wpatch16; d.wscale16 = wscale16; d.mode = ACCFLOW_CONV_F16X3; d.guard = guard;
+  d.kws = kws; d.kws_elems = 8LL * Cout * P;
+  conv_plan p;
+  if (conv_plan_direct(d, Cout > 64 ? 2 : 1, false, p)) return 1;
+  return accflow_launch_conv_direct(d, p, st);
+}
+
 extern "C" int accflow_gma_aggregate_s16(const void* attn16, const float* v, const float* fmap, long long fmap_bs,
                                          const float* gamma, float* out, long long out_bs, void* out16, long long out16_bs,
                                          void* ws, int* guard, int n, int D, int H, int W, void* stream) {
   if (!attn16 || !v || !fmap || !gamma || (!out && !out16) || !ws || n <= 0 || D <= 0 || (D & 31) || H <= 0 || W <= 0) return 1;
-  return accflow_gma_aggregate_s16_impl(attn16, v, fmap, fmap_bs, gamma, out, out_bs, out16, out16_bs, ws, guard, n, D, H, W,
-                                        as_stream(stream));
+  return gma_aggregate_s16_impl(attn16, v, fmap, fmap_bs, gamma, out, out_bs, out16, out16_bs, ws, guard, n, D, H, W,
+                                as_stream(stream));
+}
+
+// GMA attention -> S16 (gma_attn_gemm_kernel, conv2d_direct.hip): q and k are packed as fp16 hi / lo of x * 2^ASHIFT (k
+// carries GMA's scale dim_head^-1/2), two passes of the register-only GEMM per item.
+// ws: accflow_gma_attention_s16_ws_bytes(D, H, W) = two packs + partial / final column statistics.
+extern "C" long long accflow_gma_attention_s16_ws_bytes(int D, int H, int W) {
+  const long long P = (long long)H * W, Ppad = accflow_conv_coutpad((int)P), nb = (P + 127) / 128;
+  return 2 * (2LL * (D / 8) * Ppad * 16) + (nb * P * 2 + P * 2) * 4 + 256;
+}
+
+extern "C" int accflow_gma_attention_s16(const float* qk, void* attn16, void* ws, int* guard, int B, int D, int H, int W,
+                                         float scale, void* stream) {
+  if (!qk || !attn16 || !ws || B <= 0 || D < 16 || (D % 16) || H <= 0 || W <= 0) return 1;
+  const int P = H * W, Ppad = accflow_conv_coutpad(P), Kpad = accflow_conv_kpad(D, 1, 1);
+  if (Kpad != D) return 1;
+  hipStream_t st = as_stream(stream);
+  const long long pack_bytes = 2LL * (D / 8) * Ppad * 16;
+  char* kp = reinterpret_cast<char*>(ws);
+  char* qp = kp + pack_bytes;
+  float* part = reinterpret_cast<float*>(qp + pack_bytes);
+  float* stats = part + (long long)cdiv(P, 128) * P * 2;
+  const float fs = ldexpf(1.0f, ACCFLOW_F16_ASHIFT);
+  const long long item = accflow_s16_item_words(P, H, W);
+  for (int b = 0; b < B; ++b) {
+    const float* q = qk + (long long)b * 2 * D * P;   // q = qk[:, :D], k = qk[:, D:] (modules.py:63)
+    accflow_pack_kmajor(q + (long long)D * P, P, D, Kpad, Ppad, kp, scale * fs, 1, guard, st);
+    accflow_pack_kmajor(q, P, D, Kpad, Ppad, qp, fs, 1, guard, st);
+    const int rc = accflow_launch_gma_attn(kp, qp, part, stats, reinterpret_cast<unsigned*>(attn16) + b * item, 1.0f / (fs * fs),
+                                           P, D, Ppad, st);
+    if (rc) return rc;
+  }
+  ACCFLOW_RETURN_LAUNCH_STATUS();
 }
 
 extern "C" int accflow_gma_attention_f32(const float* qk, float* attn, int B, int D, int P, float scale,

@@ -2,9 +2,9 @@
 // (gma/modules.py:54-76, 102-115; heads = 1, D = 128, content branch).  The stored route (accflow_gma_attention_s16 ->
 // accflow_gma_aggregate_s16) keeps 4 P^2 bytes per distinct image1 and re-reads them in every refinement iteration; here
 // the kept state is what the softmax of a query needs to be evaluated anywhere, at any time:
-//     the fp16 hi / lo packs of q 2^ASHIFT and fp32(k scale) 2^ASHIFT (conv_pack_kmajor_kernel, 512 Ppad bytes each) and
+//     the fp16 hi / lo packs of q 2^ASHIFT and fp32(k scale) 2^ASHIFT (accflow_pack_kmajor, 512 Ppad bytes each) and
 //     the FINAL statistics {max_i, 1 / sum_i} per query (pass 0 of gma_attn_gemm_kernel + gma_attn_stats_kernel, 8 P bytes)
-// - accflow_gma_attention_alt (conv2d.hip) stops there.  Every iteration then recomputes the probabilities tile by tile
+// - accflow_gma_attention_alt (below) stops there.  Every iteration then recomputes the probabilities tile by tile
 // and feeds them to the second product from registers.
 //
 // gma_alt_aggregate_kernel<NI>: 4 waves, wave w owns the 32 queries i0 + 32 w .. + 31 of a 128-query tile for the whole
@@ -17,7 +17,7 @@
 //   3. out[d][i] += sum_j w[d][j] p[j][i]: the accumulator tile has the query on the lane and 16 keys in registers
 //      8 s .. 8 s + 7 (s = 0, 1), which IS the B fragment of a 32x32x16 product whose k slot (lane half h, element e) is key
 //      16 s + 8 (e >> 2) + 4 h + (e & 3) - so v * gamma is packed per call (gma_alt_pack_v_kernel) with its keys in that
-//      order, rows scaled by conv_pack_rows16_kernel's rule (row maximum into [2^10, 2^11)), fp16 hi + lo, and the
+//      order, rows scaled by the packs' one rule (pack_terms.h: row maximum into [2^10, 2^11)), fp16 hi + lo, and the
 //      products lo.hi, hi.lo, hi.hi accumulate into four 32 (d) x 32 (i) tiles per item (64 registers per item).
 // A wave therefore holds 32 KT + 64 NI accumulator registers for KT 32-key logit tiles and NI items: NI <= 2 items per
 // pass (one item: 128 keys at a time; two items: 64, so that two waves per SIMD still fit - at 128 keys and one wave per SIMD
@@ -34,10 +34,11 @@
 //   gma_alt_aggregate_kernel<1, 4>: 210 VGPRs, 0 AGPRs, scratch 0 bytes, 2 waves / SIMD
 //   gma_alt_aggregate_kernel<2, 2>: 216 VGPRs, 0 AGPRs, scratch 0 bytes, 2 waves / SIMD
 #include "conv_common.h"
+#include "pack_terms.h"
 
 namespace {
 
-constexpr int ALT_D = 128;          // dim_head of the estimator (the only one on the AccFlow path)
+constexpr int ALT_D = 128;         // dim_head of the estimator (the only one on the AccFlow path)
 constexpr int ALT_MAXZ = 8;
 
 __device__ __forceinline__ f32x16 alt_mfma(bf16x8 a, bf16x8 b, f32x16 c) {
@@ -45,7 +46,7 @@ __device__ __forceinline__ f32x16 alt_mfma(bf16x8 a, bf16x8 b, f32x16 c) {
 }
 
 struct gma_alt_args {
-  const void* kpack; const void* qpack;   // [2 terms][D/8][Ppad][8] fp16 (conv_pack_kmajor_kernel)
+  const void* kpack; const void* qpack;   // [2 terms][D/8][Ppad][8] fp16 (accflow_pack_kmajor)
   const float* stats;                     // [P][2] = {max, 1 / sum}
   const void* vpack;                      // this chunk's first item: [item][2 terms][Ppad/16][2 halves][128 rows][8] fp16
   float* part;                            // this chunk's first item of [Z][n][128][P]
@@ -55,57 +56,33 @@ struct gma_alt_args {
 };
 
 // v (n, 128, P) * gamma -> the second product's A fragments, one workgroup per row (item, d): the row maximum, then the
-// fp16 hi / lo of fp32(v gamma) 2^k with k from conv_pack_rows16_kernel's rule; wscale[row] = 2^-(k + ASHIFT) as there.
+// fp16 hi / lo of fp32(v gamma) 2^k with k from the packs' row-scale rule (pack_terms.h); wscale[row] = 2^-(k + ASHIFT).
 // Chunk (16-key group g, lane half h) of row d holds keys 16 g + 8 (e >> 2) + 4 h + (e & 3), e = 0..7; zero past P.
 __global__ __launch_bounds__(256) void gma_alt_pack_v_kernel(const float* __restrict__ v, int P, int Ppad,
                                                              unsigned short* __restrict__ vp, float* __restrict__ wscale,
                                                              const float* __restrict__ gptr) {
-  __shared__ float red[256];
   const int row = blockIdx.x, item = row / ALT_D, d = row - item * ALT_D;
   const float gmul = gptr[0];
   const float* src = v + (long long)row * P;
   float m = 0.0f;
   for (int j = threadIdx.x; j < P; j += 256) m = fmaxf(m, fabsf(src[j]));
-  red[threadIdx.x] = m;
-  __syncthreads();
-  for (int s2 = 128; s2 > 0; s2 >>= 1) {
-    if (threadIdx.x < s2) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s2]);
-    __syncthreads();
-  }
-  m = red[0] * fabsf(gmul);
-  int k = 0;
-  if (m > 0.0f && m < 3.0e38f) {
-    int e;
-    frexpf(m, &e);
-    k = 11 - e;
-    if (k > 100) k = 100;
-    if (k < -100) k = -100;
-  }
-  const float sc = ldexpf(1.0f, -(k + ACCFLOW_F16_ASHIFT));
+  m = pack_block_max256(m) * fabsf(gmul);
+  const float sc = pack_row_scale16(m);
   if (threadIdx.x == 0) wscale[row] = sc;
-  const float mul = ldexpf(1.0f, -ACCFLOW_F16_ASHIFT) / sc;
+  const float mul = pack_row_mul16(sc);
   const long long term_elems = (long long)Ppad * ALT_D;         // (Ppad / 16 groups x 2 halves x 128 rows x 8)
   unsigned short* dst = vp + (long long)item * 2 * term_elems;
   const int nchunk = Ppad / 8;
   for (int c = threadIdx.x; c < nchunk; c += 256) {
     const int g = c >> 1, h = c & 1;
-    unsigned short hi[8], lo[8];
+    float x[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const int j = 16 * g + 8 * (e >> 2) + 4 * h + (e & 3);
-      float rr = (j < P ? src[j] : 0.0f) * gmul * mul;
-      const _Float16 hq = (_Float16)rr;
-      rr -= (float)hq;
-      const _Float16 lq = (_Float16)rr;
-      hi[e] = __builtin_bit_cast(unsigned short, hq);
-      lo[e] = __builtin_bit_cast(unsigned short, lq);
+      x[e] = j < P ? src[j] : 0.0f;
     }
     u32x4 hv, lv;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      hv[q] = (unsigned)hi[2 * q] | ((unsigned)hi[2 * q + 1] << 16);
-      lv[q] = (unsigned)lo[2 * q] | ((unsigned)lo[2 * q + 1] << 16);
-    }
+    pack_hilo8(x, gmul, mul, hv, lv);
     const long long base = ((long long)c * ALT_D + d) * 8;
     *reinterpret_cast<u32x4*>(dst + base) = hv;
     *reinterpret_cast<u32x4*>(dst + term_elems + base) = lv;
@@ -266,6 +243,30 @@ extern "C" long long accflow_gma_attention_alt_ws_bytes(int D, int H, int W) {
   (void)D;
   const long long P = (long long)H * W, nb = (P + 127) / 128;
   return nb * P * 2 * 4 + 256;
+}
+
+// The kept state: the two packs of accflow_gma_attention_s16 per item, pass 0 and the final statistics - and no matrix.  kpack /
+// qpack: B packs of 2 * (D / 8) * coutpad(P) * 16 bytes each, stats: (B, P, 2) = {max_i, 1 / sum_i}; ws (partial
+// statistics, accflow_gma_attention_alt_ws_bytes) is free again when the call's kernels have run.
+extern "C" int accflow_gma_attention_alt(const float* qk, void* kpack, void* qpack, float* stats, void* ws, int* guard, int B,
+                                         int D, int H, int W, float scale, void* stream) {
+  if (!qk || !kpack || !qpack || !stats || !ws || B <= 0 || D != 128 || H <= 0 || W <= 0) return 1;
+  if ((long long)H * W * 512 >= (1LL << 31) - 65536) return 1;   // 32-bit offsets inside one pack (gma_alt_aggregate_kernel)
+  const int P = H * W, Ppad = accflow_conv_coutpad(P), Kpad = accflow_conv_kpad(D, 1, 1);
+  hipStream_t st = as_stream(stream);
+  const long long pack_bytes = 2LL * (D / 8) * Ppad * 16;
+  const float fs = ldexpf(1.0f, ACCFLOW_F16_ASHIFT);
+  for (int b = 0; b < B; ++b) {
+    const float* q = qk + (long long)b * 2 * D * P;
+    char* kp = reinterpret_cast<char*>(kpack) + b * pack_bytes;
+    char* qp = reinterpret_cast<char*>(qpack) + b * pack_bytes;
+    accflow_pack_kmajor(q + (long long)D * P, P, D, Kpad, Ppad, kp, scale * fs, 1, guard, st);
+    accflow_pack_kmajor(q, P, D, Kpad, Ppad, qp, fs, 1, guard, st);
+    const int rc = accflow_launch_gma_attn_stats(kp, qp, reinterpret_cast<float*>(ws), stats + (long long)b * 2 * P,
+                                                 1.0f / (fs * fs), P, D, Ppad, st);
+    if (rc) return rc;
+  }
+  ACCFLOW_RETURN_LAUNCH_STATUS();
 }
 
 // ws of accflow_gma_aggregate_alt: the v pack, its row scales, the partial sums of the key splits

@@ -30,7 +30,7 @@ USE_H16_STATE = os.environ.get("ACCFLOW_H16_STATE", "1") == "1"
 
 
 def h16_state_supported():
-    """The pre-split-only state rides on the tap-specialised 5-tap kernels of the direct route (csrc/conv2d.hip).  The library
+    """The pre-split-only state rides on the tap-specialised 5-tap kernels of the direct route (csrc/conv2d_direct.hip).  The library
     decides which route is on (ops.conv_gru16_supported: its switches, read once per process) and refuses a packed-operand
     descriptor where it is off, so Python asks it instead of re-reading the switches; S16_VIA_MULTI is the Python-only part."""
     return not ops.S16_VIA_MULTI and ops.conv_gru16_supported()

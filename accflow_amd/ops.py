@@ -22,7 +22,7 @@ ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH = 0, 1, 2, 3
 CONV_F32, CONV_BF16X3, CONV_BF16X6, CONV_F16X3 = 0, 2, 3, 4
 _MODES = {"f32": CONV_F32, "bf16x3": CONV_BF16X3, "bf16x6": CONV_BF16X6, "f16x3": CONV_F16X3}
 # arithmetic of the MFMA conv kernel: exact fp32 MFMA, or fp32 operands split into 2 / 3 bf16 terms on
-# the bf16 matrix cores with fp32 accumulation (see csrc/conv2d.hip).
+# the bf16 matrix cores with fp32 accumulation (see csrc/conv2d.hip; the operand packs: csrc/conv_pack.hip).
 # Default f16x3: the direct conv kernel splits every fp32 operand into fp16 hi + lo of x * 2^s (3 MFMAs per product;
 # 22 significant bits per operand thanks to power-of-two row / activation scales, see include/accflow_hip.h; measured
 # 2.4e-5 px EPE vs the reference on C3) with a range guard - see with_range_guard(); every other kernel then runs bf16x6.

@@ -314,7 +314,7 @@ def instantiations(row):
     if fam == STEM:
         return [("conv_stem.hip", "stem")]
     co = 2 if row.cout <= 2 else 4
-    return [("conv2d.hip", "%s<%d>" % ("small_patch" if fam == SMALL_PATCH else "small", co))]
+    return [("conv_small.hip", "%s<%d>" % ("small_patch" if fam == SMALL_PATCH else "small", co))]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -661,11 +661,11 @@ def test_table_is_complete():
         assert got == S16M_ARGS[f], (f, got)
         for a in got:
             assert (f, a) in tabled, (f, a)
-    # the <= 4-channel kernels and the stem: accflow_conv2d_f32 launches them itself
-    conv = src("conv2d.hip")
+    # the <= 4-channel kernels (accflow_launch_conv_small) and the stem
+    conv = src("conv_small.hip")
     for co in (2, 4):
-        assert conv.count("hipLaunchKernelGGL((conv2d_small_cout_kernel<%d>)" % co) == 1 and ("conv2d.hip", "small<%d>" % co) in tabled
-        assert conv.count("hipLaunchKernelGGL((conv2d_small_cout_patch_kernel<%d>)" % co) == 1 and ("conv2d.hip", "small_patch<%d>" % co) in tabled
+        assert conv.count("hipLaunchKernelGGL((conv2d_small_cout_kernel<%d>)" % co) == 1 and ("conv_small.hip", "small<%d>" % co) in tabled
+        assert conv.count("hipLaunchKernelGGL((conv2d_small_cout_patch_kernel<%d>)" % co) == 1 and ("conv_small.hip", "small_patch<%d>" % co) in tabled
     assert len(re.findall(r"hipLaunchKernelGGL\(\(conv2d_small_cout", conv)) == 4
     assert ("conv_stem.hip", "stem") in tabled
     # the restated launch rules: the lines they restate

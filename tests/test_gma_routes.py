@@ -1,5 +1,5 @@
-"""Every arithmetic route of GMA's attention and global-motion aggregation (csrc/gma.hip and the two dispatchers in
-csrc/conv2d.hip, accflow_gma_aggregate_conv / accflow_gma_aggregate_s16_impl) against float64 references written HERE:
+"""Every arithmetic route of GMA's attention and global-motion aggregation (csrc/gma.hip with its two dispatchers
+gma_aggregate_conv / gma_aggregate_s16_impl, on the packs of csrc/conv_pack.hip) against float64 references written HERE:
 softmax_j(scale * q_i . k_j) and fmap + gamma * attn @ v, plain torch on the CPU.
 
 Routes (restated by att_route / agg_route below, pinned to the sources by test_host_thresholds_are_the_ones_restated_here):
@@ -182,18 +182,18 @@ def test_host_thresholds_are_the_ones_restated_here():
     assert "constexpr int U = 8;" in gma and gma.count("for (int j = wave; j < P; j += 16 * U) {") == 2
     assert "hipLaunchKernelGGL(col_softmax16_kernel, dim3(cdiv(P, 64), B), dim3(1024), 0, st, attnT, P);" in gma
     assert "if (mode == ACCFLOW_CONV_F32) return 1;" in gma
-    conv = src(*csrc, "conv2d.hip")
-    assert "if (mode == ACCFLOW_CONV_F16X3 && B == 1 && P >= 16) {" in conv
-    assert "const bool f16 = mode == ACCFLOW_CONV_F16X3 && (P % 64) == 0;" in conv
-    assert "if (mode == ACCFLOW_CONV_F16X3 && !f16) mode = ACCFLOW_CONV_BF16X6;" in conv
-    assert "if (P % 64 == 0) {" in conv and "if (D <= 32) return 1;" in conv
-    assert "if (conv_plan_direct(d, D > 64 ? 2 : 1, false, p)) return 1;" in conv
-    assert "if (conv_plan_direct(d, Cout > 64 ? 2 : 1, false, p)) return 1;" in conv
-    assert conv.count("return accflow_launch_conv_direct(d, p, st);") == 3
-    assert "d.kws = kws; d.kws_elems = 8LL * D * P;" in conv and "d.kws = kws; d.kws_elems = 8LL * Cout * P;" in conv
-    assert "if (B == 1) { d.kws = kws; d.kws_elems = 8LL * D * P; }" in conv
-    assert "constexpr int ROWS16_REG = %d;" % ROWS16_REG in conv
-    assert "const bool inreg = nchunk <= ROWS16_REG * 256 && !(Cin & 3);" in conv
+    conv, pack = src(*csrc, "conv2d.hip"), src(*csrc, "conv_pack.hip")
+    assert "if (mode == ACCFLOW_CONV_F16X3 && B == 1 && P >= 16) {" in gma
+    assert "const bool f16 = mode == ACCFLOW_CONV_F16X3 && (P % 64) == 0;" in gma
+    assert "if (mode == ACCFLOW_CONV_F16X3 && !f16) mode = ACCFLOW_CONV_BF16X6;" in gma
+    assert "if (P % 64 == 0) {" in gma and "if (D <= 32) return 1;" in gma
+    assert "if (conv_plan_direct(d, D > 64 ? 2 : 1, false, p)) return 1;" in gma
+    assert "if (conv_plan_direct(d, Cout > 64 ? 2 : 1, false, p)) return 1;" in gma
+    assert gma.count("return accflow_launch_conv_direct(d, p, st);") + conv.count("return accflow_launch_conv_direct(d, p, st);") == 3
+    assert "d.kws = kws; d.kws_elems = 8LL * D * P;" in gma and "d.kws = kws; d.kws_elems = 8LL * Cout * P;" in gma
+    assert "if (B == 1) { d.kws = kws; d.kws_elems = 8LL * D * P; }" in gma
+    assert "constexpr int ROWS16_REG = %d;" % ROWS16_REG in pack
+    assert "const bool inreg = nchunk <= ROWS16_REG * 256 && !(Cin & 3);" in pack
     # the routing thresholds have one home, the plan unit: one split-K rule and one tail-split rule for every kernel family
     plan = src(*csrc, "conv_plan.cpp")
     assert "return (K + 31) / 32 * 32;" in plan
@@ -213,7 +213,8 @@ def test_host_thresholds_are_the_ones_restated_here():
     assert plan.count("if (fill > best + 0.03) { best = fill; Z = z; }") == 1
     direct = src(*csrc, "conv2d_direct.hip")
     bf = src(*csrc, "conv2d_bf16s_kernel.h")
-    for text in (conv, direct, bf, src(*csrc, "conv2d_s16m.hip")):       # ... and no launcher decides any of it again
+    moved = [src(*csrc, f) for f in ("conv_small.hip", "corr_volume.hip", "gma_alt.hip")]   # (what conv2d.hip held until the split)
+    for text in [conv, gma, pack, direct, bf, src(*csrc, "conv2d_s16m.hip")] + moved:       # ... and no launcher decides any of it again
         assert "fill > best" not in text and "< 320" not in text and "< 700" not in text and "getenv(\"ACCFLOW_DIRECT" not in text
     # the products the split kernels keep: a = weights, b = activations, terms (2,0) (0,2) (1,1) only with three terms
     for line in ("c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2][tc], b[0][tp], c, 0, 0, 0);",
