@@ -104,6 +104,7 @@ SIGNATURES = {
     "accflow_corr_volume_ws_bytes": [c_i, c_i, c_i],
     "accflow_corr_volume_split_f32": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f],
     "accflow_corr_lookup_f32": [c_f, c_f, c_f, c_f, c_f, c_f, c_ll, c_i, c_i, c_i, c_f],
+    "accflow_corr_lookup_r3_f32": [c_f, c_f, c_f, c_f, c_f, c_f, c_ll, c_i, c_i, c_i, c_f],
     "accflow_corr_disp_supported": [c_i, c_i],
     "accflow_corr_disp_level_elems": [c_i, c_i, c_i],
     "accflow_corr_volume_disp_f32": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_f],
@@ -126,6 +127,7 @@ SIGNATURES = {
     "accflow_compose_flow_f32": [c_f, c_ll, c_f, c_ll, c_f, c_ll, c_i, c_i, c_i, c_f],
     "accflow_get_occ_f32": [c_f, c_ll, c_f, c_ll, c_f, c_ll, c_f, c_ll, c_i, c_i, c_i, c_i, c_i, c_f],
     "accflow_downflow8_f32": [c_f, c_f, c_i, c_i, c_i, c_i, c_f],
+    "accflow_upflow8_f32": [c_f, c_ll, c_f, c_ll, c_i, c_i, c_i, c_f],
     "accflow_forward_interpolate_f32": [c_f, c_f, c_i, c_i, c_i, c_f],
     "accflow_instance_norm_f32": [c_f, c_f, c_f, c_i, c_i, c_i, ctypes.c_float, c_i, c_f],
     "accflow_split_tanh_relu_f32": [c_f, c_f, c_ll, c_f, c_ll, c_i, c_i, c_i, c_i, c_f],

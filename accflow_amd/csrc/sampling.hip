@@ -341,6 +341,50 @@ extern "C" int accflow_downflow8_f32(const float* flow, float* out, int B, int C
   ACCFLOW_RETURN_LAUNCH_STATUS();
 }
 
+// upflow8 (raft/utils/utils.py:90-93): 8 * F.interpolate(flow, size=(8h, 8w), bilinear, align_corners=True), the output of
+// an update block without a mask head (RAFT-small).  Output row Y reads source row Y (h-1) / (8h-1): quotient and remainder
+// are taken in integers, so the fraction r / (8h-1) is one correctly rounded division (a float product of the scale and Y
+// is off by ~Y ulps, which the interpolation multiplies by the difference of two neighbours).  One thread = 4 consecutive
+// output pixels of one row, stored as one 16-byte word: a wave writes 1 KiB of one output row segment (8w % 8 == 0 and
+// 16-byte aligned batch items keep every word aligned).
+namespace {
+__global__ __launch_bounds__(256) void upflow8_kernel(const float* __restrict__ flow, long long flow_bs, float* __restrict__ out,
+                                                      long long out_bs, int B, int h, int w) {
+  const int H = 8 * h, W = 8 * w, W4 = 2 * w;
+  const long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= (long long)B * 2 * H * W4) return;
+  const int x4 = (int)(g % W4);
+  const long long t = g / W4;
+  const int Y = (int)(t % H);
+  const int bc = (int)(t / H), b = bc >> 1, c = bc & 1;
+  const int dy = H - 1, dx = W - 1;
+  const int ny = Y * (h - 1), y0 = ny / dy, y1 = min(y0 + 1, h - 1);
+  const float ly = (float)(ny - y0 * dy) / (float)dy, hy = 1.0f - ly;
+  const float* p0 = flow + b * flow_bs + (long long)c * h * w + (long long)y0 * w;
+  const float* p1 = p0 + (long long)(y1 - y0) * w;
+  float v[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int nx = (4 * x4 + k) * (w - 1), x0 = nx / dx, x1 = min(x0 + 1, w - 1);
+    const float lx = (float)(nx - x0 * dx) / (float)dx, hx = 1.0f - lx;
+    const float s = __builtin_fmaf(p1[x1], ly * lx, __builtin_fmaf(p1[x0], ly * hx, __builtin_fmaf(p0[x1], hy * lx, p0[x0] * (hy * hx))));
+    v[k] = 8.0f * s;
+  }
+  float* o = out + b * out_bs + ((long long)c * H + Y) * W + 4 * x4;
+  *reinterpret_cast<f32x4*>(o) = f32x4{v[0], v[1], v[2], v[3]};
+}
+}  // namespace
+
+extern "C" int accflow_upflow8_f32(const float* flow, long long flow_bs, float* out, long long out_bs, int B, int h, int w,
+                                   void* stream) {
+  // (h, w <= 8192: row / column numerators Y (h-1) stay far inside an int; out and out_bs keep the 16-byte stores aligned)
+  if (!flow || !out || B <= 0 || h <= 0 || w <= 0 || h > 8192 || w > 8192 || (reinterpret_cast<uintptr_t>(out) & 15) || (out_bs & 3))
+    return 1;
+  const long long n = (long long)B * 2 * (8 * h) * (2 * w);
+  hipLaunchKernelGGL(upflow8_kernel, dim3(cdiv(n, 256)), dim3(256), 0, as_stream(stream), flow, flow_bs, out, out_bs, B, h, w);
+  ACCFLOW_RETURN_LAUNCH_STATUS();
+}
+
 // Deformable convolution, first half: the deformed im2col "columns" of torchvision.ops.deform_conv2d (modulated,
 // one offset group, stride 1; AccFlow_.py:104): cols[b][tap*C + c][y][x] = m_tap * bilinear(x[b][c], y + ky - padH +
 // dy_tap, x + kx - padW + dx_tap), dy first; the whole sample is 0 when h <= -1 || h >= H || w <= -1 || w >= W and

@@ -19,9 +19,9 @@ LAYOUT = os.environ.get("ACCFLOW_CORR_LAYOUT", "disp")
 
 class CorrBlock:
     def __init__(self, fmap1, fmap2, num_levels=4, radius=4):
-        if num_levels != 4 or radius != 4:
-            raise NotImplementedError("HIP CorrBlock is built for the reference's fixed 4 levels / radius 4 "
-                                      "(raft.py:39-40, gma.py:21-22)")
+        if num_levels != 4 or radius not in (3, 4):
+            raise NotImplementedError("HIP CorrBlock is built for the reference's 4 levels and radius 4 (raft.py:39-40, "
+                                      "gma.py:21-22) or radius 3 (RAFT-small, raft.py:33-34)")
         require_cuda(fmap1, fmap2)
         self.num_levels = num_levels
         self.radius = radius
@@ -30,8 +30,9 @@ class CorrBlock:
         # Measured on MI355X, B = 11 pairs at 60x128 (us per lookup launch): row-major 112-116 whatever the flow;
         # displaced 40 for coherent flow, 52 in the benchmark, ~115 for pure noise (a 4x8-tiled layout measured 135 and was removed).  The displaced volume
         # needs a split conv mode (its level 0 comes out of the matrix-core GEMM's displaced-store epilogue).
+        # Radius 3 is looked up in the row-major pyramid (csrc/corr_lookup.hip), whatever LAYOUT says.
         def build():
-            if LAYOUT == "disp" and ops.current_mode() != ops.CONV_F32 and ops.corr_disp_supported(H8, W8):
+            if radius == 4 and LAYOUT == "disp" and ops.current_mode() != ops.CONV_F32 and ops.corr_disp_supported(H8, W8):
                 return ops.corr_volume_disp(fmap1, fmap2)
             return ops.corr_volume(fmap1, fmap2)
         # (stand-alone use: the f16x3 volume is rebuilt in bf16x6 if a feature left the fp16 split's range; inside an
@@ -53,7 +54,7 @@ class CorrBlock:
         return self._pyr if isinstance(self._pyr, list) else self._pyr.to_rowmajor()
 
     def supports_s16(self):
-        return isinstance(self._pyr, ops.DispPyramid)
+        return self.radius == 4 and isinstance(self._pyr, ops.DispPyramid)
 
     def lookup_s16(self, coords, out16, cache=None):
         """The lookup written pre-split for convc1's S16 pack (ops.corr_lookup_s16); cache: see ops.conv2d."""
@@ -72,7 +73,7 @@ class CorrBlock:
 
     def __call__(self, coords, out=None):
         require_cuda(coords)
-        return ops.corr_lookup(self._pyr, coords.float().contiguous(), out=out)
+        return ops.corr_lookup(self._pyr, coords.float().contiguous(), out=out, radius=self.radius)
 
     @staticmethod
     def corr(fmap1, fmap2):
@@ -89,7 +90,8 @@ class AlternateCorrBlock:
 
     def __init__(self, fmap1, fmap2, num_levels=4, radius=4):
         if num_levels != 4 or radius != 4:
-            raise NotImplementedError("HIP AlternateCorrBlock is built for the reference's fixed 4 levels / radius 4")
+            raise NotImplementedError("HIP AlternateCorrBlock is built for the reference's fixed 4 levels / radius 4 "
+                                      "(radius 3, RAFT-small: use CorrBlock)")
         require_cuda(fmap1, fmap2)
         if fmap1.shape != fmap2.shape:
             raise RuntimeError("AlternateCorrBlock: fmap1 %s and fmap2 %s differ" % (tuple(fmap1.shape), tuple(fmap2.shape)))

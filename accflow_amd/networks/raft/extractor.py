@@ -1,4 +1,4 @@
-"""BasicEncoder / ResidualBlock on HIP kernels.
+"""BasicEncoder / ResidualBlock and RAFT-small's SmallEncoder / BottleneckBlock on HIP kernels.
 
 Parameter layout (names, shapes, the norm3 <-> downsample[1] sharing) follows the reference's
 networks/raft/extractor.py:5-63 (ResidualBlock) and :115-225 (BasicEncoder) so its checkpoints load
@@ -157,6 +157,125 @@ class ResidualBlock(nn.Module):
             x = ops.conv2d(packs.conv(tag + ".ds", self.downsample[0], bn=self.norm3 if bn else None), x)
         return ops.conv2d(packs.conv(tag + ".c2", self.conv2, bn=self.norm2 if bn else None), y,
                           act=ops.ACT_RELU, epi=ops.EPI_RES_RELU, e0=x)
+
+
+class BottleneckBlock(nn.Module):
+    """RAFT-small's block (reference extractor.py:66-134): 1x1 to planes/4, 3x3 (the strided one), 1x1 back to planes,
+    each followed by norm + ReLU, and the closing relu(x + y) with a projected x where the block strides.  fp32 NCHW
+    activations in every conv mode; norm_fn "instance" / "none"."""
+
+    def __init__(self, in_planes, planes, norm_fn="group", stride=1):
+        super().__init__()
+        self.norm_fn = norm_fn
+        self.conv1 = nn.Conv2d(in_planes, planes // 4, kernel_size=1, padding=0)
+        self.conv2 = nn.Conv2d(planes // 4, planes // 4, kernel_size=3, padding=1, stride=stride)
+        self.conv3 = nn.Conv2d(planes // 4, planes, kernel_size=1, padding=0)
+        self.relu = nn.ReLU(inplace=True)
+        widths = (planes // 4, planes // 4, planes) + ((planes,) if stride != 1 else ())
+        for k, ch in enumerate(widths, start=1):
+            setattr(self, "norm%d" % k, _make_norm(norm_fn, ch, planes // 8))
+        self.downsample = None
+        if stride != 1:
+            self.downsample = nn.Sequential(nn.Conv2d(in_planes, planes, kernel_size=1, stride=stride), self.norm4)
+
+    def _norm_relu_conv(self, y, st, norm, pk):
+        """conv(relu(norm(y))) with statistics of its own output: the normalisation rides in the convolution's patch loader
+        where the planned kernel can do that, and is a pass over y otherwise."""
+        r = None
+        if st is not None and ops.USE_NORM_ON_LOAD:
+            r = ops.conv2d(pk, y, want_stats=True, in_norm=ops.instance_stats_finalize(st, norm.eps))
+        if r is None:
+            ops.instance_norm(y, 1, eps=norm.eps, stats=st)
+            r = ops.conv2d(pk, y, want_stats=True)
+        return r
+
+    def run(self, x, packs, tag):
+        kind = self.norm_fn
+        if kind not in ("instance", "none"):
+            raise NotImplementedError("BottleneckBlock: norm_fn %r is not on the RAFT-small inference path "
+                                      "(instance: fnet, none: cnet)" % (kind,))
+        pk1, pk2, pk3 = (packs.conv(tag + ".c%d" % k, getattr(self, "conv%d" % k)) for k in (1, 2, 3))
+        if kind == "instance":
+            y, st = ops.conv2d(pk1, x, want_stats=True)
+            y, st = self._norm_relu_conv(y, st, self.norm1, pk2)
+            y, st = self._norm_relu_conv(y, st, self.norm2, pk3)
+            if self.downsample is not None:
+                x, st4 = ops.conv2d(packs.conv(tag + ".ds", self.downsample[0]), x, want_stats=True)
+                ops.instance_norm(x, 0, eps=self.norm4.eps, stats=st4)
+            return ops.instance_norm(y, 2, res=x, eps=self.norm3.eps, stats=st)      # relu(x + relu(norm3(y)))
+        y = ops.conv2d(pk1, x, act=ops.ACT_RELU)
+        y = ops.conv2d(pk2, y, act=ops.ACT_RELU)
+        if self.downsample is not None:
+            x = ops.conv2d(packs.conv(tag + ".ds", self.downsample[0]), x)
+        return ops.conv2d(pk3, y, act=ops.ACT_RELU, epi=ops.EPI_RES_RELU, e0=x)
+
+
+def _init_encoder(module):
+    for m in module.modules():
+        if isinstance(m, nn.Conv2d):
+            nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+        elif isinstance(m, (nn.BatchNorm2d, nn.InstanceNorm2d, nn.GroupNorm)):
+            if m.weight is not None:
+                nn.init.constant_(m.weight, 1)
+            if m.bias is not None:
+                nn.init.constant_(m.bias, 0)
+
+
+class SmallEncoder(nn.Module):
+    """RAFT-small's encoder (reference extractor.py:228-306): a 32-channel 7x7 stem, three pairs of BottleneckBlocks
+    (32, 64, 96 channels; 1/2, 1/4, 1/8 resolution), a 1x1 head.  Same parameter names as the reference; a list of frames
+    runs as one batch and comes back as views of one frame-major tensor (any number of frames, where the reference
+    splits into two)."""
+
+    def __init__(self, output_dim=128, norm_fn="batch", dropout=0.0):
+        super().__init__()
+        self.norm_fn = norm_fn
+        self.norm1 = _make_norm(norm_fn, 32, 8)
+        self.conv1 = nn.Conv2d(3, 32, kernel_size=7, stride=2, padding=3)
+        self.relu1 = nn.ReLU(inplace=True)
+        prev = 32
+        for idx, (wd, st) in enumerate(zip((32, 64, 96), (1, 2, 2)), start=1):
+            setattr(self, "layer%d" % idx, nn.Sequential(BottleneckBlock(prev, wd, norm_fn, stride=st),
+                                                         BottleneckBlock(wd, wd, norm_fn, stride=1)))
+            prev = wd
+        self.in_planes = prev
+        self.dropout = nn.Dropout2d(p=dropout) if dropout > 0 else None
+        self.conv2 = nn.Conv2d(prev, output_dim, kernel_size=1)
+        _init_encoder(self)
+        self._packs = PackCache()
+
+    def forward(self, x):
+        if self.norm_fn not in ("instance", "none"):
+            raise NotImplementedError("SmallEncoder: norm_fn %r is not on the RAFT-small inference path "
+                                      "(instance: fnet, none: cnet)" % (self.norm_fn,))
+        if self.training and self.dropout is not None:
+            raise RuntimeError("SmallEncoder: the HIP path is inference-only (call .eval()); dropout is a training "
+                               "feature outside the AccFlow inference path")
+        require_cuda(*(x if isinstance(x, (tuple, list)) else (x,)))
+        return self._encode(x)
+
+    @torch.no_grad()
+    @ops.range_guarded
+    def _encode(self, x):
+        is_list = isinstance(x, (tuple, list))
+        if is_list:
+            batch_dim = x[0].shape[0]
+            x = span(x)
+        require_cuda(x)
+        x = x.float().contiguous()
+        pk = self._packs
+        if self.norm_fn == "instance":
+            x, st = ops.conv2d(pk.conv("stem", self.conv1), x, want_stats=True)
+            ops.instance_norm(x, 1, eps=self.norm1.eps, stats=st)
+        else:
+            x = ops.conv2d(pk.conv("stem", self.conv1), x, act=ops.ACT_RELU)
+        for li in (1, 2, 3):
+            for bi, blk in enumerate(getattr(self, "layer%d" % li)):
+                x = blk.run(x, pk, "l%d.%d" % (li, bi))
+        x = ops.conv2d(pk.conv("head", self.conv2), x)
+        if is_list:
+            x = torch.split(x, batch_dim, dim=0)
+        return x
 
 
 class BasicEncoder(nn.Module):

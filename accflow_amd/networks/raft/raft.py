@@ -23,9 +23,9 @@ from ... import ops
 from .._packs import require_cuda
 from . import corr as _corr
 from .corr import AlternateCorrBlock, CorrBlock
-from .extractor import BasicEncoder
+from .extractor import BasicEncoder, SmallEncoder
 from . import update as _update
-from .update import BasicUpdateBlock, UpdateWorkspace
+from .update import BasicUpdateBlock, SmallUpdateBlock, UpdateWorkspace
 
 
 import os
@@ -63,24 +63,34 @@ def _side_streams(device, n):
 
 class RAFT(nn.Module):
     KEEP_CONTEXT_RUNS = False     # (RAFTGMA: items out of one image1 share an attention matrix and stay in one pair group)
+    small = False                 # (set per instance by RAFT.__init__: args.small, the reference's RAFT-small)
 
     def __init__(self, args):
         super().__init__()
         self.args = args
-        if getattr(args, "small", False):
-            raise NotImplementedError("RAFT-small is not reachable from networks.build_flow_estimator "
-                                      "(networks/__init__.py:8 fixes small=False)")
-        self.hidden_dim = hdim = 128
-        self.context_dim = cdim = 128
-        args.corr_levels = 4
-        args.corr_radius = 4
+        self.small = bool(getattr(args, "small", False))
+        if self.small:       # RAFT-small (raft.py:30-34, 49-56): RAFT(small_args()); build_flow_estimator fixes small=False
+            self.hidden_dim = hdim = 96
+            self.context_dim = cdim = 64
+            args.corr_levels = 4
+            args.corr_radius = 3
+        else:
+            self.hidden_dim = hdim = 128
+            self.context_dim = cdim = 128
+            args.corr_levels = 4
+            args.corr_radius = 4
         if "dropout" not in self.args:
             self.args.dropout = 0
         if "alternate_corr" not in self.args:
             self.args.alternate_corr = False
-        self.fnet = BasicEncoder(output_dim=256, norm_fn="instance", dropout=args.dropout)
-        self.cnet = BasicEncoder(output_dim=hdim + cdim, norm_fn="batch", dropout=args.dropout)
-        self.update_block = BasicUpdateBlock(self.args, hidden_dim=hdim)
+        if self.small:
+            self.fnet = SmallEncoder(output_dim=128, norm_fn="instance", dropout=args.dropout)
+            self.cnet = SmallEncoder(output_dim=hdim + cdim, norm_fn="none", dropout=args.dropout)
+            self.update_block = SmallUpdateBlock(self.args, hidden_dim=hdim)
+        else:
+            self.fnet = BasicEncoder(output_dim=256, norm_fn="instance", dropout=args.dropout)
+            self.cnet = BasicEncoder(output_dim=hdim + cdim, norm_fn="batch", dropout=args.dropout)
+            self.update_block = BasicUpdateBlock(self.args, hidden_dim=hdim)
 
     def freeze_bn(self):
         for m in self.modules():
@@ -102,7 +112,15 @@ class RAFT(nn.Module):
 
     def _alternate(self):
         """alternate_corr (raft.py:45-46), read at forward time: AlternateCorrBlock instead of the correlation volume."""
-        return ALTERNATE_CORR or bool(getattr(self.args, "alternate_corr", False))
+        alt = ALTERNATE_CORR or bool(getattr(self.args, "alternate_corr", False))
+        if alt and self.small:
+            raise NotImplementedError("alternate_corr is built for radius 4: RAFT-small (radius 3) looks up the correlation volume")
+        return alt
+
+    def _workspace(self, B, h, w, dev):
+        if self.small:
+            return self.update_block.workspace(B, h, w, dev)
+        return UpdateWorkspace(B, h, w, dev, hidden=self.hidden_dim, x_dim=self._x_dim())
 
     def _prepack(self):
         """All weight packs the refinement loop uses, built on the current (main) stream before the fork."""
@@ -220,7 +238,7 @@ class RAFT(nn.Module):
                     st.wait_event(ctx_ready)  # the context features and the update block's packs (split mode: no flow_init)
                 elif early:
                     st.wait_stream(main)      # the context features, the update block's packs, flow_init
-                ws = UpdateWorkspace(b1 - b0, h, w, dev, hidden=self.hidden_dim, x_dim=self._x_dim())
+                ws = self._workspace(b1 - b0, h, w, dev)
                 self._prepare_context(ws, (cnet_feat[0], cnet_feat[1][b0:b1]) if indexed else cnet_feat[b0:b1],
                                       ctx_ids[b0:b1] if ctx_ids is not None else None)
                 fi = flow_init[b0:b1] if flow_init is not None else None
@@ -236,7 +254,10 @@ class RAFT(nn.Module):
                 if forked is not None and early:
                     st.wait_event(forked)
                 ops.flow_from_coords(coords1, dst0=ws.flow)
-                ops.convex_upsample(ws.flow, masks[g], out=out_all[bounds[g][0]:bounds[g][1]])
+                if masks[g] is None:     # an update block without a mask head (RAFT-small): upflow8, raft.py:139-140
+                    ops.upflow8(ws.flow, out=out_all[bounds[g][0]:bounds[g][1]])
+                else:
+                    ops.convex_upsample(ws.flow, masks[g], out=out_all[bounds[g][0]:bounds[g][1]])
                 if return_low:
                     low_all[bounds[g][0]:bounds[g][1]].copy_(ws.flow)
             if st != main:
@@ -357,6 +378,8 @@ class RAFT(nn.Module):
 
     def _packs_usable(self, feats, pairs):
         fb = feats.get("fmap_base")
+        if self.small:     # (the per-frame operand packs feed the displaced radius-4 pyramid)
+            return False
         return (fb is not None and USE_CORR_PACKS and not self._alternate() and _corr.LAYOUT == "disp" and all(f in fb[1] for p in pairs for f in p)
                 and ops.corr_packs_supported(fb[0].shape[1], fb[0].shape[2], fb[0].shape[3]))
 
@@ -441,3 +464,9 @@ class RAFT(nn.Module):
 
 def default_args():
     return argparse.Namespace(small=False, mixed_precision=True)
+
+
+def small_args():
+    """RAFT-small (990 162 parameters; hidden 96, context 64, radius 3, bottleneck encoders, ConvGRU, bilinear upflow8):
+    RAFT(small_args()).  networks.build_flow_estimator keeps the reference's small=False."""
+    return argparse.Namespace(small=True, mixed_precision=True)

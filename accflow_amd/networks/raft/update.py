@@ -165,6 +165,137 @@ def _ws_net32(ws):
 UpdateWorkspace.net32 = _ws_net32
 
 
+class ConvGRU(nn.Module):
+    """The non-separable GRU of RAFT-small (reference update.py:16-31): three 3x3 convolutions over cat[h, x]."""
+
+    def __init__(self, hidden_dim=128, input_dim=192 + 128):
+        super().__init__()
+        for gate in "zrq":
+            setattr(self, "conv" + gate, nn.Conv2d(hidden_dim + input_dim, hidden_dim, 3, padding=1))
+        self.hidden_dim = hidden_dim
+        self.input_dim = input_dim
+
+
+class SmallMotionEncoder(nn.Module):
+    def __init__(self, args):
+        super().__init__()
+        cor_planes = args.corr_levels * (2 * args.corr_radius + 1) ** 2
+        self.convc1 = nn.Conv2d(cor_planes, 96, 1, padding=0)
+        self.convf1 = nn.Conv2d(2, 64, 7, padding=3)
+        self.convf2 = nn.Conv2d(64, 32, 3, padding=1)
+        self.conv = nn.Conv2d(128, 80, 3, padding=1)
+
+
+class SmallUpdateWorkspace:
+    """UpdateWorkspace of RAFT-small: hidden 96, context 64, 4 x 49 lookup channels, fp32 NCHW in every conv mode (the
+    pre-split S16 chain is BasicUpdateBlock's).  One channel-sliced buffer holds the GRU's operands, so that no torch.cat runs:
+
+        HX (B, 242, h, w) = [ h (96) | inp (64) | motion (80) , flow (2) ]       x = HX[:, 96:]"""
+    HIDDEN, CONTEXT, MOTION, LOOKUP = 96, 64, 80, 196
+    s16 = False
+
+    def __init__(self, B, h, w, device):
+        def buf(c):
+            return torch.empty((B, c, h, w), dtype=torch.float32, device=device)
+        hd, cd, md = self.HIDDEN, self.CONTEXT, self.MOTION
+        self.B, self.h, self.w, self.hidden, self.x_dim = B, h, w, hd, cd + md + 2
+        self.descs = {}
+        self.hx = buf(hd + self.x_dim)
+        self.net = self.hx[:, :hd]
+        self.inp = self.hx[:, hd:hd + cd]
+        self.motion_conv = self.hx[:, hd + cd:hd + cd + md]
+        self.motion_flow = self.hx[:, hd + cd + md:]
+        self.x = self.hx[:, hd:]
+        self.z, self.rh = buf(hd), buf(hd)
+        self.flow = buf(2)
+        self.flow16 = buf(16)          # row-shifted stack of the flow (input of convf1 as a 1x7 conv)
+        self.corr = buf(self.LOOKUP)
+        self.corflo = buf(128)         # [relu(convc1) (96) | relu(convf2) (32)]
+        self.f1 = buf(64)
+        self.head = buf(128)
+
+    def net32(self):
+        return self.net.contiguous()
+
+
+class SmallUpdateBlock(nn.Module):
+    """RAFT-small's update block (reference update.py:99-112): SmallMotionEncoder -> ConvGRU -> FlowHead(96, 128), no mask
+    head.  Every convolution is an ops.conv2d on fp32 tensors: z and r stacked as ONE 3x3 convolution of 192 channels whose
+    epilogue writes z and r*h, q with the state update in its epilogue (both over the two sources [h or r*h | x]), the flow
+    head's second convolution accumulating into coords1."""
+
+    def __init__(self, args, hidden_dim=96):
+        super().__init__()
+        self.encoder = SmallMotionEncoder(args)
+        self.gru = ConvGRU(hidden_dim=hidden_dim, input_dim=82 + 64)
+        self.flow_head = FlowHead(hidden_dim, hidden_dim=128)
+        self._packs = PackCache()
+
+    def workspace(self, B, h, w, device):
+        if self.gru.hidden_dim != SmallUpdateWorkspace.HIDDEN:
+            raise NotImplementedError("SmallUpdateBlock: the workspace is laid out for hidden_dim 96 (raft.py:31)")
+        return SmallUpdateWorkspace(B, h, w, device)
+
+    def _gru_packs(self):
+        pk, g = self._packs, self.gru
+        return (pk.conv_cat("zr", [g.convz, g.convr], C0=g.hidden_dim), pk.conv("q", g.convq, C0=g.hidden_dim))
+
+    def prepack(self):
+        """Every weight pack of the block on the CURRENT stream (see BasicUpdateBlock.prepack)."""
+        pk, e, f = self._packs, self.encoder, self.flow_head
+        pk.conv("c1", e.convc1); pk.conv("f1s", e.convf1, rows_as_channels=True); pk.conv("f2", e.convf2); pk.conv("cf", e.conv)
+        self._gru_packs()
+        pk.conv("fh1", f.conv1); pk.conv("fh2", f.conv2)
+
+    def motion_encoder(self, ws):
+        """SmallMotionEncoder.forward (update.py:71-77): ws.corr, ws.flow16 -> ws.motion_conv (the flow slice beside it is
+        written by flow_from_coords)."""
+        pk, e, R = self._packs, self.encoder, ops.ACT_RELU
+        ops.conv2d(pk.conv("c1", e.convc1), ws.corr, out=ws.corflo[:, :96], act=R)
+        # convf1 (7x7 over the 2-channel flow) as a 1x7 convolution of the 16-channel row-shifted stack: same products
+        ops.conv2d(pk.conv("f1s", e.convf1, rows_as_channels=True), ws.flow16, out=ws.f1, act=R, algo_cin=2 * 7)
+        ops.conv2d(pk.conv("f2", e.convf2), ws.f1, out=ws.corflo[:, 96:], act=R)
+        ops.conv2d(pk.conv("cf", e.conv), ws.corflo, out=ws.motion_conv, act=R)
+
+    def gru_step(self, ws):
+        """ConvGRU.forward (update.py:23-31), h updated in place in ws.hx."""
+        zr, q = self._gru_packs()
+        ops.conv2d(zr, ws.net, in1=ws.x, out=ws.z, act=ops.ACT_SIGMOID, epi=ops.EPI_GRU_ZR, e0=ws.net, out2=ws.rh)
+        ops.conv2d(q, ws.rh, in1=ws.x, out=ws.net, act=ops.ACT_TANH, epi=ops.EPI_GRU_Q, e0=ws.net, e1=ws.z)
+
+    def flow_delta(self, ws, coords1=None, out=None):
+        """FlowHead (update.py:13-14).  With coords1 the delta is accumulated in place (raft.py:136)."""
+        pk, f = self._packs, self.flow_head
+        ops.conv2d(pk.conv("fh1", f.conv1), ws.net, out=ws.head, act=ops.ACT_RELU)
+        if coords1 is not None:
+            return ops.conv2d(pk.conv("fh2", f.conv2), ws.head, out=coords1, epi=ops.EPI_ACCUM, e0=coords1)
+        return ops.conv2d(pk.conv("fh2", f.conv2), ws.head, out=out)
+
+    def step(self, ws, coords1, want_mask):
+        """One refinement iteration on the workspace: expects ws.corr and ws.flow16 / ws.motion_flow set.  There is no
+        mask head: returns None whatever want_mask says, and the caller upsamples with ops.upflow8 (raft.py:139-140)."""
+        self.motion_encoder(ws)
+        self.gru_step(ws)
+        self.flow_delta(ws, coords1=coords1)
+        return None
+
+    @torch.no_grad()
+    @ops.range_guarded
+    def forward(self, net, inp, corr, flow):
+        """Reference signature (update.py:106-112): returns (net, None, delta_flow)."""
+        require_cuda(net, inp, corr, flow)
+        B, _, h, w = net.shape
+        ws = self.workspace(B, h, w, net.device)
+        ops.copy_into(net.float(), ws.net)
+        ops.copy_into(inp.float(), ws.inp)
+        ops.copy_into(corr.float(), ws.corr)
+        ops.flow_from_coords(flow.float().contiguous(), dst0=ws.flow, dst1=ws.motion_flow, stack16=ws.flow16, is_flow=True)
+        self.motion_encoder(ws)
+        self.gru_step(ws)
+        delta = self.flow_delta(ws)
+        return ws.net32(), None, delta
+
+
 class BasicUpdateBlock(nn.Module):
     def __init__(self, args, hidden_dim=128, input_dim=128):
         super().__init__()

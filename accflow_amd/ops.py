@@ -1022,7 +1022,8 @@ def deform_conv2d_s16(pk, x, offset, dmask, out16, mask_is_logit=False):
 
 
 LOOKUP_BYTES_PER_PX = 4 * 100 * 4 + 8 + 324 * 4  # = 2904, SURVEY.md 8(d)
-LOOKUP_S16_CHANNELS = 4 * 88   # S16 lookup output: 88 channels per level (81 taps in (row, column) order + 7 zeros)
+LOOKUP_R3_BYTES_PER_PX = 4 * 64 * 4 + 8 + 196 * 4  # = 1816: the radius-3 lookup (8x8 windows, 4 x 49 taps)
+LOOKUP_S16_CHANNELS = 4 * 88  # S16 lookup output: 88 channels per level (81 taps in (row, column) order + 7 zeros)
 
 
 def corr_pyramid_shapes(H8, W8, levels=4):
@@ -1278,10 +1279,15 @@ def corr_lookup_alt_s16(pairs, coords, out16, cache=None):
                    cache, out16, (pairs, coords, out16))
 
 
-def corr_lookup(pyramid, coords, out=None):
+def corr_lookup(pyramid, coords, out=None, radius=4):
+    """radius 3 (RAFT-small; row-major pyramid only): (B, 4 * 49, H8, W8) instead of (B, 4 * 81, H8, W8)."""
+    if radius not in (3, 4):
+        raise NotImplementedError("corr_lookup: radius 4 or 3, got %r" % (radius,))
     if isinstance(pyramid, DispPyramid):
+        if radius != 4:
+            raise NotImplementedError("corr_lookup: the displacement-indexed pyramid is looked up at radius 4 only")
         return _corr_lookup_alt(pyramid, coords, out, "accflow_corr_lookup_disp_f32")
-    return _corr_lookup_rowmajor(pyramid, coords, out)
+    return _corr_lookup_rowmajor(pyramid, coords, out, radius)
 
 
 def _corr_lookup_alt(pyr, coords, out, entry):
@@ -1405,15 +1411,24 @@ def flow_from_coords_s16(coords1, dst0, dst1, stack16, motion16, motion_ch, is_f
             (coords1, dst0, dst1, stack16, motion16))
 
 
-def _corr_lookup_rowmajor(pyramid, coords, out=None):
+def _corr_lookup_rowmajor(pyramid, coords, out=None, radius=4):
     lib = _lib.load()
     coords = _dense(coords, "coords")
     B, _, H8, W8 = coords.shape
+    taps = 4 * (2 * radius + 1) ** 2
     if out is None:
-        out = torch.empty((B, 324, H8, W8), dtype=torch.float32, device=coords.device)
+        out = torch.empty((B, taps, H8, W8), dtype=torch.float32, device=coords.device)
     out_bs = _plane4(out, "out")
-    for t in pyramid:
-        _dense(t, "pyramid level")
+    if tuple(out.shape) != (B, taps, H8, W8):
+        raise RuntimeError("corr_lookup: out shape %s != %s" % (tuple(out.shape), (B, taps, H8, W8)))
+    for t, (hl, wl) in zip(pyramid, corr_pyramid_shapes(H8, W8)):
+        if _dense(t, "pyramid level").numel() != B * H8 * W8 * hl * wl:
+            raise RuntimeError("corr_lookup: pyramid level %s does not belong to coords %s" % (tuple(t.shape), tuple(coords.shape)))
+    if radius == 3:
+        # algorithmic bytes: 4 levels x 8x8 fp32 window + 8 B coords + 196 fp32 written per px
+        return _launch(lib.accflow_corr_lookup_r3_f32, (_p(pyramid[0]), _p(pyramid[1]), _p(pyramid[2]), _p(pyramid[3]), _p(coords),
+                                                        _p(out), out_bs, B, H8, W8),
+                       "accflow_corr_lookup_r3_f32", ("corr_lookup", lambda: (LOOKUP_R3_BYTES_PER_PX * B * H8 * W8, "r3")), ret=out)
     # algorithmic bytes: 4 levels x 10x10 fp32 window + 8 B coords + 324 fp32 written per px
     return _launch(lib.accflow_corr_lookup_f32, (_p(pyramid[0]), _p(pyramid[1]), _p(pyramid[2]), _p(pyramid[3]), _p(coords),
                                                  _p(out), out_bs, B, H8, W8),
@@ -1432,6 +1447,25 @@ def convex_upsample(flow, mask, out=None):
         raise RuntimeError("convex_upsample: out must be a contiguous (B,2,8*H8,8*W8) tensor (a batch slice is fine)")
     _check(lib.accflow_convex_upsample_f32(_p(flow), fbs, _p(mask), mbs, _p(out), B, H8, W8, _stream()),
            "accflow_convex_upsample_f32")
+    return out
+
+
+def upflow8(flow, out=None):
+    """8 * F.interpolate(flow, size=(8h, 8w), mode="bilinear", align_corners=True) (raft/utils/utils.py:90-93): the full-resolution
+    flow of an update block without a mask head.  flow: (B, 2, h, w); out: a contiguous (B, 2, 8h, 8w) tensor (a batch slice
+    is fine)."""
+    lib = _lib.load()
+    fbs = _plane4(flow, "flow")
+    B, C, h, w = flow.shape
+    if C != 2:
+        raise RuntimeError("upflow8: flow must be (B,2,h,w)")
+    if out is None:
+        out = torch.empty((B, 2, 8 * h, 8 * w), dtype=torch.float32, device=flow.device)
+    elif tuple(out.shape) != (B, 2, 8 * h, 8 * w) or not out.is_contiguous():
+        raise RuntimeError("upflow8: out must be a contiguous (B,2,8*h,8*w) tensor (a batch slice is fine)")
+    obs = _plane4(out, "out")
+    _launch(lib.accflow_upflow8_f32, (_p(flow), fbs, _p(out), obs, B, h, w), "accflow_upflow8_f32",
+            ("upflow8", lambda: (4.0 * B * 2 * h * w * 65, "B%d %dx%d" % (B, h, w))))
     return out
 
 

@@ -313,6 +313,12 @@ int accflow_corr_volume_split_f32(const float* fmap1, const float* fmap2, float*
 int accflow_corr_lookup_f32(const float* lvl0, const float* lvl1, const float* lvl2,
                             const float* lvl3, const float* coords, float* out, long long out_bs,
                             int B, int H8, int W8, void* stream);
+/* The same lookup at radius 3 (RAFT-small, raft/raft.py:30-34), same arithmetic on the same row-major pyramid:
+ * out[b, l*49 + i*7 + j, y, x] = bilinear_zeros(lvl_l[b,y,x], cx/2^l + i-3, cy/2^l + j-3); out: (B, 196, H8, W8), batch
+ * stride out_bs (a channel slice of a larger buffer is fine). */
+int accflow_corr_lookup_r3_f32(const float* lvl0, const float* lvl1, const float* lvl2,
+                               const float* lvl3, const float* coords, float* out, long long out_bs,
+                               int B, int H8, int W8, void* stream);
 
 /* Displacement-indexed variants (the layout the estimators use on the hot path; same lookup results).  Level l is
  * E_l[b][p/128][dy][dx][p%128] with p = y1*W8 + x1 the query pixel (blocks of 128, the last one zero-padded),
@@ -417,6 +423,10 @@ int accflow_get_occ_s16(const float* flow, long long flow_bs, const float* i1, l
 
 /* downflow8 (AccFlow_.py:138-142): bilinear align_corners resize to (H/8, W/8), then / 8. */
 int accflow_downflow8_f32(const float* flow, float* out, int B, int C, int H, int W, void* stream);
+/* upflow8 (raft/utils/utils.py:90-93; RAFT-small's output, raft/raft.py:139-140): out = 8 * bilinear align_corners resize of
+ * flow (B,2,h,w), batch stride flow_bs, to (B,2,8h,8w), batch stride out_bs (a batch slice of a larger tensor is fine; `out`
+ * 16-byte aligned, out_bs % 4 == 0).  h, w <= 8192. */
+int accflow_upflow8_f32(const float* flow, long long flow_bs, float* out, long long out_bs, int B, int h, int w, void* stream);
 /* forward_interpolate (raft/utils/utils.py:31-63): nearest kept source of the flow pushed along itself; flow, out (B,2,H8,W8), not overlapping. */
 int accflow_forward_interpolate_f32(const float* flow, float* out, int B, int H8, int W8, void* stream);
 
