@@ -757,9 +757,11 @@ __device__ __forceinline__ void corr_disp_store(const accflow_conv_desc& d, f32x
 // corr_disp_store (half h = row 2*yo + h at a time through T[c][p]); the 2x2 mean of level 1 - F.avg_pool2d(2, 2) on
 // the volume's last two dims, raft/corr.py:20-22 - needs (2yo, 2k), (2yo, 2k+1), (2yo+1, 2k), (2yo+1, 2k+1) of ONE
 // query pixel p: the first two are summed while half 0 sits in LDS (S0[k][p] = a + b), the other two added while half 1
-// does: ((a + b) + c) + d, then * 0.25 - the order corr_disp_pool_kernel uses, so the result is bit-identical to
-// pooling the stored level 0 (the accumulator scale `osc` is a power of two and commutes with the sums).  This removes
-// the pooling pass that re-read the whole level 0 (2.6 GB per C3 step).
+// does: ((a + b) + c) + d, then * 0.25 - the order corr_disp_pool_kernel uses.  Every tap is multiplied by the accumulator
+// scale `osc` BEFORE it is summed (no contraction into an FMA), i.e. a, b, c, d are the very fp32 values level 0 stores,
+// so the result is bit-identical to pooling the stored level 0 for ANY osc: the per-pair calls pass a power of two (which
+// would commute with the sums), the per-frame packs (1 / sqrt(C)) / 2^8, a power of two only for C a power of four.  This
+// removes the pooling pass that re-read the whole level 0 (2.6 GB per C3 step).
 // Level-1 stores: lane -> p = ph*64 + lane, k = (c + lane/2) mod 32 for the wave-uniform (ph, c): x1 and 2k advance
 // together (W8 even), so dx1 = (xc*32 + k) - (x1 >> 1) is constant along the lanes and the 64 lanes write 256
 // contiguous bytes of E_1[p/128][dy1][dx1][p%128]; the LDS reads (pitch 132) are bank-conflict free.
@@ -816,13 +818,14 @@ __device__ __forceinline__ void corr_disp_store2(const accflow_conv_desc& d, f32
     if (pool_row) {
 #pragma unroll 4
       for (int it = 0; it < 16; ++it) {
+#pragma clang fp contract(off)  // the scaled taps are rounded to fp32 as level 0 stores them: no FMA with the sums
         const int n = wave * 16 + it;
         const int pl = (n & 1) * 64 + lane, k = ((n >> 1) + (lane >> 1)) & 31;
-        const float a = T[(2 * k) * DISP_PITCH + pl], b = T[(2 * k + 1) * DISP_PITCH + pl];
+        const float a = T[(2 * k) * DISP_PITCH + pl] * osc, b = T[(2 * k + 1) * DISP_PITCH + pl] * osc;
         if (h == 0) {
           S0[k * DISP_PITCH + pl] = a + b;
         } else {
-          const float v = (((S0[k * DISP_PITCH + pl] + a) + b) * osc) * 0.25f;
+          const float v = ((S0[k * DISP_PITCH + pl] + a) + b) * 0.25f;
           const int t = tab[pl];
           const int xo = xc * 32 + k;
           int dy = yo - ((t >> 16) >> 1), dx = xo - ((t & 0xFFFF) >> 1);

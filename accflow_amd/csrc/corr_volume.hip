@@ -276,7 +276,8 @@ extern "C" int accflow_corr_volume_disp_f32(const float* fmap1, const float* fma
   const int rc = accflow_corr_level0_bf16s(fmap1, fmap2, lvl0, ws, B, C, H8, W8, mode, 1, guard, as_stream(stream), lvl1,
                                            &lvl1_done);
   if (rc) return rc;
-  // the register-only GEMM wrote level 1 with level 0 (bit-identical to pooling level 0): pool from level 1 on
+  // the direct GEMM wrote level 1 with level 0 - bit-identical to pooling the stored level 0 whatever the accumulator
+  // scale, since corr_disp_store2 scales every tap before it sums: pool from level 1 on
   return accflow_corr_disp_pool_from(lvl0, lvl1, lvl2, lvl3, B, H8, W8, lvl1_done ? 1 : 0, as_stream(stream));
 }
 

@@ -4,6 +4,8 @@ digests: tests/golden/pack_bytes_parent.json.
 The recorded file was written, on the GPU, by the commit BEFORE the pack kernels moved to csrc/conv_pack.hip and their numeric
 rules to csrc/pack_terms.h; tests/test_pack_bytes.py holds every later library to it.  Every case runs twice; a case whose
 two runs disagree is not recorded: it is listed under "_unstable" and left to the tolerance tests of its route.
+"_rerecorded" (written by hand, not by this script) names the digests that were replaced later, and why: a change of
+results made on purpose replaces exactly the digests it explains and leaves the others as first recorded.
 
     python tests/golden/make_pack_bytes_golden.py [OUT]     # rewrite the JSON (only ever from the commit it records)
 """

@@ -5,6 +5,10 @@ tests/golden/pack_bytes_parent.json holds, for every case of tests/pack_bytes_ca
 as the parent commit wrote it on the GPU (tests/golden/make_pack_bytes_golden.py; every case was run twice there and
 recorded only when both runs agreed).  test_fused_pack_equals_the_single_purpose_packs compares two paths that share the
 rules, so it cannot see a mistake made in the shared rule; this one can.
+Recorded again since ("_rerecorded" in the file says which and why): levels 1..3 of the four corr_volume_disp_packed cases,
+whose C = 32 makes the accumulator scale no power of two - the level-1 emission of corr_disp_store2 scales every tap
+before it sums since tests/test_corr_routes.py holds it to the pool of the stored level 0; their lvl0 and packs digests,
+and every other case, are the first recording's.
 
 Cases: the five single-purpose pack entry points and accflow_conv_pack_all_f32 (plain and transpose_flip) on the eight
 shapes of that test, accflow_conv_pack_multi16 on three sources, accflow_corr_pack_f32 in the three split modes (one input
