@@ -470,22 +470,24 @@ class AccFlow(nn.Module):
 
     @torch.no_grad()
     @ops.range_guarded
-    def fuse_chain(self, images, by_pair, ctx=None):
+    def fuse_chain(self, images, by_pair, ctx=None, return_small=False):
         """The sequential part of AccFlow.forward: by_pair[(i, j)] = (N,2,H/8,W/8) flow i -> j.  ctx: the context
-        encoder's outputs if the caller computed them already (context_async / context_join)."""
+        encoder's outputs if the caller computed them already (context_async / context_join).  return_small: (outputs, the
+        decoder's 1/8-resolution flow of the LAST step) - what the next step of a longer chain starts from (AccFlowStream);
+        the launches are the same either way."""
         if ctx is None:
             ctx = self.context([im.float().contiguous() for im in images], want16=True)
         if getattr(_CHAIN_TLS, "no_ksplit", False):      # (chain_in_pipeline / pipeline_chain_arithmetic: the chain proper only)
             with ops.ksplit_scope(False):
-                return self._fuse_chain(images, by_pair, ctx)
-        return self._fuse_chain(images, by_pair, ctx)
+                return self._fuse_chain(images, by_pair, ctx, return_small)
+        return self._fuse_chain(images, by_pair, ctx, return_small)
 
-    def _fuse_chain(self, images, by_pair, ctx):
+    def _fuse_chain(self, images, by_pair, ctx, return_small=False):
         n = len(images)
         ctx, ctx16 = ctx
         outs, F2n = [], by_pair[(1, 0)]
         if ctx16 is not None and ops.s16_active() and USE_S16_CHAIN and _hoist_now() and n > 3:
-            return self._fuse_chain_hoisted(n, by_pair, ctx, ctx16)
+            return self._fuse_chain_hoisted(n, by_pair, ctx, ctx16, return_small)
         defer = ctx16 is not None and ops.s16_active() and USE_S16_CHAIN and USE_CHAIN_DEFER_UP and n > 3
         if defer:
             # Only the 1/8-resolution flow of step i enters step i+1 (AccFlow_.py:171-175): the mask head and the convex
@@ -501,9 +503,9 @@ class AccFlow(nn.Module):
             outs.append(up)
         if defer:
             outs = list(self.flow_decoder.upsample16(x16_all, small_all).split(N, dim=0))
-        return outs
+        return (outs, F2n) if return_small else outs
 
-    def _fuse_chain_hoisted(self, n, by_pair, ctx, ctx16):
+    def _fuse_chain_hoisted(self, n, by_pair, ctx, ctx16, return_small=False):
         """fuse_chain with what does not depend on the accumulated flow F2n taken out of the sequential loop and batched over
         the n - 2 steps (AccFlow_.py:191-200 per step: flow_ini, dflow, the context features - hence the occlusion map, the
         error map and the blending mask - are known once the estimator has run): FlowEncoder over [flow_ini, dflow] of all
@@ -544,7 +546,7 @@ class AccFlow(nn.Module):
                 outs.append(up)
         if defer:
             outs = list(self.flow_decoder.upsample16(x16_all, small_all).split(N, dim=0))
-        return outs
+        return (outs, F2n) if return_small else outs
 
     @torch.no_grad()
     @ops.range_guarded
@@ -604,6 +606,29 @@ class AccFlow(nn.Module):
         # first without a host synchronisation per stage; only if some value left the fp16 split's range, stage by stage
         out, tripped = ops.optimistic(run, images[0].device)
         return run() if tripped else out
+
+    def accumulate_video(self, frames, chunk=1, iters=None):
+        """Generator over an iterable of frames (each (N,3,H,W), scaled as forward() expects): yields (i, F(i -> 0)) for
+        i = 2, 3, ... as the frames come, `chunk` frames per AccFlowStream.push - memory does not grow with the video."""
+        if int(chunk) != chunk or chunk < 1:
+            raise ValueError("accumulate_video: chunk must be an integer >= 1 (got %r)" % (chunk,))
+        stream = AccFlowStream(self, iters=iters)
+
+        def gen():
+            batch = []
+            for f in frames:
+                batch.append(f)
+                if len(batch) == chunk:
+                    yield from flush(batch)
+                    batch = []
+            if batch:
+                yield from flush(batch)
+
+        def flush(batch):
+            outs = stream.push(batch)
+            return zip(range(stream.n_frames - len(outs), stream.n_frames), outs)
+
+        return gen()
 
     @torch.no_grad()
     def forward_pair_sharded_stream(self, sequences, group=None, on_result=None):
@@ -702,3 +727,192 @@ class AccFlow(nn.Module):
         shares = hasattr(getattr(self, "ofe", None), "att")
         return run_pair_sharded(est, fuse, len(images), self.pair_schedule(len(images)), dst=dst, group=group,
                                 keep_together=shares)
+
+
+def _own(t):
+    """t without the rest of the allocation it is a view of (one frame's slice of a batched encoder output keeps the whole
+    batch alive otherwise)."""
+    if isinstance(t, ops.S16):
+        return ops.S16(_own(t.data), t.C)
+    return t if t.untyped_storage().nbytes() == t.numel() * t.element_size() else t.clone()
+
+
+class _StreamState:
+    """What AccFlowStream carries from one push to the next: frame 0 and the last frame - image, fnet features, context
+    features (fp32, and pre-split where the mode has them) - the accumulated 1/8-resolution flow last -> 0, and the conv mode
+    the features were made in.  Nothing here grows with the number of frames pushed."""
+    __slots__ = ("images", "fmap", "ctx", "ctx16", "F2n", "mode")
+
+    def __init__(self, images, fmap, ctx, ctx16, F2n, mode):
+        self.images, self.fmap, self.ctx, self.ctx16 = list(images), list(fmap), list(ctx), ctx16
+        self.F2n, self.mode = F2n, mode
+
+    def features(self):
+        """A fresh estimate_pairs feature dict (encode_frames clears one whose mode differs: never hand out the state's own)."""
+        return {"fmap": dict(enumerate(self.fmap)), "cnet": {}, "mode": self.mode}
+
+
+class AccFlowStream:
+    """Backward accumulation over a frame stream: push frames as they come, get F(i -> 0) back, at constant memory.
+
+        s = AccFlowStream(model)            # model: AccFlow, any estimator; iters: the estimator's iterations (None: forward's)
+        flows = s.push(frames)              # one (N,3,H,W) tensor or a list of them -> [F(i -> 0) for each pushed i >= 2]
+
+    A push of frames a..b is AccFlow.forward on [frame 0, frame a-1, frame a, ..., frame b] with pair (1, 0) of that list
+    - F(a-1 -> 0) - not estimated: it is the flow carried from the previous push, the decoder's 1/8-resolution output of its
+    last step (what the reference hands from step to step, AccFlow_.py:171-175,200).  Frames 0 and a-1 are not encoded again
+    either (fnet and context features are kept; only image2 roles occur for them, so no cnet).  The launches are
+    estimate_small's and fuse_chain's; with model.warm_start the push follows forward_warm's schedule instead.  The first
+    push that brings the stream to three frames is forward() on all of them.  A push that raises leaves the stream as it was.
+    With N > 1 the encoders run sample by sample (_encode_per_sample), everything else batched."""
+
+    def __init__(self, model, iters=None):
+        if not hasattr(model.ofe, "estimate_pairs"):
+            raise TypeError("AccFlowStream: the estimator must take estimate_pairs(features=) - its encoder outputs of frame 0 "
+                            "and of the last frame are kept from push to push")
+        self.model, self.iters = model, iters
+        self.reset()
+
+    def reset(self):
+        self._pending, self._state, self._like, self.n_frames = [], None, None, 0
+
+    def _checked(self, frames):
+        frames = [frames] if isinstance(frames, torch.Tensor) else list(frames)
+        like = self._like
+        for f in frames:
+            if not (isinstance(f, torch.Tensor) and f.dim() == 4 and f.shape[1] == 3):
+                raise ValueError("AccFlowStream.push: frames are (N,3,H,W) tensors")
+            require_cuda(f)
+            if like is None:
+                like = (tuple(f.shape), f.device)
+            if (tuple(f.shape), f.device) != like:
+                raise ValueError("AccFlowStream.push: frame %s on %s in a stream of %s on %s" % (tuple(f.shape), f.device, *like))
+        return frames, like
+
+    @torch.no_grad()
+    def push(self, frames):
+        frames, like = self._checked(frames)
+        if not frames:
+            return []
+        st = self._state
+        if st is None and len(self._pending) + len(frames) < 3:      # frames 0 and 1 alone: nothing to accumulate yet
+            self._pending = self._pending + [f.float().clone() for f in frames]
+            self._like, self.n_frames = like, len(self._pending)
+            return []
+        run = self._push_warm if self.model.warm_start else self._push
+        outs, state = run(st, list(st.images if st is not None else self._pending), frames)
+        self._state, self._pending, self._like = state, [], like     # (the one commit, after the run whose result is returned)
+        self.n_frames += len(frames)
+        return outs
+
+    def _push(self, st, kept, new):
+        m = self.model
+        new = m.stack_frames(new)
+        L = kept + new
+        N, dev = L[0].shape[0], L[0].device
+        pairs = m.pair_schedule(len(L))
+        if st is not None:
+            pairs.remove((1, 0))
+
+        def run():
+            mode = ops.current_mode()
+            cached = st is not None and st.mode == mode
+            todo = new if cached else L        # (another conv mode than the cache's: frames 0 and a-1 again, from the images)
+            feats = st.features() if st is not None else {}
+            if N > 1:
+                ctx, ctx16 = self._encode_per_sample(L, pairs, range(len(L) - len(todo), len(L)), feats, want16=True)
+                small = m.estimate_small(L, pairs, iters=self.iters, features=feats)
+            else:
+                handle = m.context_async(todo) if CONTEXT_SIDE_STREAM else None
+                small = m.estimate_small(L, pairs, iters=self.iters, features=feats)
+                if handle is not None:
+                    ctx, ctx16 = m.context_join(handle)
+                else:
+                    ctx, ctx16 = m.context([im.float().contiguous() for im in todo], want16=True)
+            ctx, ctx16 = list(ctx), list(ctx16) if ctx16 is not None else None
+            if cached:
+                ctx = st.ctx + ctx
+                ctx16 = st.ctx16 + ctx16 if ctx16 is not None and st.ctx16 is not None else None
+            by_pair = {p: small[k * N:(k + 1) * N] for k, p in enumerate(pairs)}
+            if st is not None:
+                by_pair[(1, 0)] = st.F2n
+            outs, F2n = m.fuse_chain(L, by_pair, ctx=(ctx, ctx16), return_small=True)
+            return outs, (feats["fmap"], ctx, ctx16, F2n, mode)
+
+        # as forward(): first without a host synchronisation per stage; stage by stage only if a value left the fp16 range
+        out, tripped = ops.optimistic(run, dev)
+        outs, made = run() if tripped else out
+        return outs, self._next_state(st, L, *made)
+
+    def _push_warm(self, st, kept, new):
+        """forward_warm's schedule: the adjacent pairs of the new frames in one batch, then per frame the compose_flow seed,
+        the seeded estimate i -> 0 and the fusion step."""
+        m = self.model
+        L = kept + [f.float() for f in new]
+        N, dev = L[0].shape[0], L[0].device
+        adjacent = [(i, i - 1) for i in range(1 if st is None else 2, len(L))]
+        warm_iters = m.warm_iters if m.warm_iters is not None else self.iters
+
+        def run():
+            mode = ops.current_mode()
+            cached = st is not None and st.mode == mode
+            feats = st.features() if st is not None else {}
+            if N > 1:
+                ctx = self._encode_per_sample(L, adjacent + [(i, 0) for i in range(2, len(L))],
+                                              range(2 if cached else 0, len(L)), feats, want16=False)[0]
+            small = m.estimate_small(L, adjacent, iters=self.iters, features=feats)
+            adj = {p: small[k * N:(k + 1) * N] for k, p in enumerate(adjacent)}
+            if N == 1:
+                ctx = list(m.context([im.float().contiguous() for im in (L[2:] if cached else L)]))
+            if cached:
+                ctx = st.ctx + ctx
+            outs, F2n = [], adj[(1, 0)] if st is None else st.F2n
+            for i in range(2, len(L)):
+                dflow = adj[(i, i - 1)].contiguous()
+                seed = ops.compose_flow(dflow, F2n.contiguous())
+                flow_ini = m.estimate_small(L, [(i, 0)], flow_init=seed, iters=warm_iters, features=feats)
+                F2n, up = m._fuse(dflow, flow_ini.contiguous(), F2n.contiguous(), ctx[i], ctx[i - 1], ctx[0])
+                outs.append(up)
+            return outs, (feats["fmap"], ctx, None, F2n, mode)
+
+        outs, made = ops.with_range_guard(run, dev, name="AccFlowStream.push")
+        return outs, self._next_state(st, L, *made)
+
+    def _encode_per_sample(self, L, pairs, ctx_ids, feats, want16):
+        """N > 1: the three encoders sample by sample, so that a sample's flows do not depend on what else is in the batch.
+        The convolution planner's schedule (split-K, tile shapes) is a function of the images per encoder call, and a
+        last-bit difference in an encoder output grows past 1e-4 px over the refinement and the chain (measured: 1.5e-4 to
+        2.3e-4 px between N = 2 and N = 1 with batched encoders, at most 6.3e-5 this way); the refinement and the chain stay
+        batched.  Fills `feats` with what
+        estimate_pairs needs for `pairs` (the samples' outputs joined per frame) and returns the context encoder's outputs of
+        frames `ctx_ids` in context()'s two forms."""
+        m = self.model
+        fnet_ids, cnet_ids = {i for p in pairs for i in p}, {i for i, _ in pairs}
+        per, ctx, ctx16 = [], [], []
+        for n in range(L[0].shape[0]):
+            frames = [f[n:n + 1] for f in L]
+            fn = {k: ({i: t[n:n + 1] for i, t in v.items()} if isinstance(v, dict) else v) for k, v in feats.items()}
+            per.append(m.ofe.encode_frames(frames, fnet_ids, cnet_ids, fn))
+            c = m.context([frames[i].float().contiguous() for i in ctx_ids], want16=want16)
+            c, c16 = c if want16 else (c, None)
+            ctx.append(c)
+            ctx16.append(c16)
+        feats.clear()
+        feats.update({key: {i: torch.cat([p[key][i] for p in per]) for i in per[0][key]} for key in ("fmap", "cnet")})
+        feats["mode"] = per[0]["mode"]
+        joined = [torch.cat(cs) for cs in zip(*ctx)]
+        if any(c is None for c in ctx16):
+            return joined, None
+        return joined, [ops.S16(torch.cat([c.data for c in cs]), cs[0].C) for cs in zip(*ctx16)]
+
+    @staticmethod
+    def _next_state(st, L, fmap, ctx, ctx16, F2n, mode):
+        """Frame 0 and the last frame of L as the next push's cache; what the old state holds of frame 0 in this mode stays."""
+        last = len(L) - 1
+        if st is not None and st.mode == mode:
+            fmap0, ctx0 = st.fmap[0], st.ctx[0]
+        else:
+            fmap0, ctx0 = _own(fmap[0]), _own(ctx[0])
+        return _StreamState([L[0] if st is not None else L[0].clone(), L[last].clone()], [fmap0, _own(fmap[last])],
+                            [ctx0, _own(ctx[last])], [_own(ctx16[0]), _own(ctx16[last])] if ctx16 is not None else None,
+                            _own(F2n.float()), mode)
