@@ -155,6 +155,10 @@ SIGNATURES = {
     "accflow_gma_aggregate_alt": [c_f, c_f, c_f, c_f, c_f, c_ll, c_f, c_f, c_ll, c_f, c_ll, c_f, c_f, c_i, c_i, c_i, c_i, c_f],
     "accflow_gma_aggregate_t_f32": [c_f, c_f, c_f, c_f, c_f, c_ll, c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_f],
     "accflow_gma_aggregate_f32": [c_f, c_f, c_f, c_f, c_f, c_ll, c_i, c_i, c_i, c_f],
+    "accflow_gma_pos_tables_f32": [c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, ctypes.c_float, c_f],
+    "accflow_gma_attention_pos_f32": [c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, ctypes.c_float, c_f],
+    "accflow_gma_attention_pos_ws_bytes": [c_i, c_i, c_i, c_i, c_i],
+    "accflow_gma_attention_pos_t": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, ctypes.c_float, c_f],
     "accflow_act_backward_f32": [c_f, c_ll, c_f, c_ll, c_f, c_ll, c_i, c_ll, c_i, c_f],
     "accflow_add_f32": [c_f, c_ll, c_f, c_ll, c_i, c_ll, c_f],
     "accflow_l1_grad_f32": [c_f, c_f, c_f, c_ll, ctypes.c_float, c_f],
@@ -172,6 +176,7 @@ RETURNS_LONGLONG = frozenset((
     "accflow_gma_aggregate_ws_bytes", "accflow_gma_attention_ws_bytes", "accflow_gma_aggregate_s16_ws_bytes",
     "accflow_gma_attention_s16_ws_bytes", "accflow_gma_attention_alt_ws_bytes", "accflow_gma_aggregate_alt_ws_bytes",
     "accflow_corr_disp_level_elems", "accflow_corr_alt_pyramid_elems", "accflow_s16_item_words",
+    "accflow_gma_attention_pos_ws_bytes",
 ))
 
 _lock = threading.Lock()

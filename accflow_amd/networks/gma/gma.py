@@ -1,5 +1,6 @@
 """RAFT + Global Motion Aggregation (reference networks/gma/gma.py:14-125) on gfx950 kernels.
 Same forward signature and state_dict; execution notes as in raft/raft.py."""
+import argparse
 import os
 
 import torch.nn as nn
@@ -43,8 +44,12 @@ class RAFTGMA(RAFT):
         flag): the aggregation recomputes the attention's probabilities in every iteration instead of reading a stored
         matrix.  It runs in the default mode (fp16 split, S16 activations: ops.s16_active()); in fp32 mode, with
         ACCFLOW_S16=0 and in the range guard's bf16x6 retry of a stage (ops.guard_report() names it) the stored matrix
-        runs as without the switch."""
+        runs as without the switch.  So does a positional model (args.position_only / args.position_and_content): the
+        no-matrix route has no positional term, and _prepare_context keeps such a model on the stored matrix."""
         return ALTERNATE_ATTENTION or bool(getattr(self.args, "alternate_attention", False))
+
+    def _positional(self):
+        return bool(getattr(self.args, "position_only", False) or getattr(self.args, "position_and_content", False))
 
     def _prepack(self):
         super()._prepack()
@@ -72,7 +77,7 @@ class RAFTGMA(RAFT):
                 else:
                     runs.append([slot[key], b, b + 1])
             inp = inp[reps].contiguous()
-        if self._alternate_attention() and ops.s16_active():
+        if self._alternate_attention() and ops.s16_active() and not self._positional():
             ws.attention = self.att.forward_alt(inp, runs=runs)
             return
         ws.attention = self.att.forward_t(inp, runs=runs)
@@ -80,3 +85,12 @@ class RAFTGMA(RAFT):
     def _iteration(self, ws, corr_fn, coords1, last):
         self._lookup_and_flow(ws, corr_fn, coords1)
         return self.update_block.step(ws, coords1, want_mask=last, attention=ws.attention)
+
+
+def gma_args(position_only=False, position_and_content=False):
+    """The factory's GMA arguments (networks.build_flow_estimator keeps both flags False, as the reference does) with the
+    attention variant chosen: RAFTGMA(gma_args(position_only=True)) takes the logits from the relative position embeddings
+    alone, RAFTGMA(gma_args(position_and_content=True)) adds them to the content logits.  position_only wins when both are
+    set (modules.py:62-68)."""
+    return argparse.Namespace(num_heads=1, mixed_precision=True, position_only=bool(position_only),
+                              position_and_content=bool(position_and_content))

@@ -1,9 +1,12 @@
 """GMA attention / aggregation on HIP kernels (reference networks/gma/modules.py).
 
-Only the content branch exists on the AccFlow path: build_flow_estimator fixes position_only =
-position_and_content = False and num_heads = 1 (networks/__init__.py:14-19).  RelPosEmb is kept as a
-parameter/buffer container because its tensors are part of the reference state_dict
-(`att.pos_emb.rel_ind`, `.rel_height.weight`, `.rel_width.weight`) even though they are never evaluated.
+build_flow_estimator fixes position_only = position_and_content = False and num_heads = 1
+(networks/__init__.py:14-19): the content branch.  The two positional variants (modules.py:6-31, 62-68) are built with
+RAFTGMA(gma_args(position_only=True)) / RAFTGMA(gma_args(position_and_content=True)): RelPosEmb holds the reference's
+tensors (`att.pos_emb.rel_ind`, `.rel_height.weight`, `.rel_width.weight`), and Attention evaluates the two embedding
+weights as h + w dot products per query (ops.gma_pos_tables: sim_pos[i, j] = A[i, u] + Bw[i, v]) which the softmax
+kernels add to the content logits - or take as the whole logit.  `rel_ind` is never gathered: the kernels index the
+weights by u - x + M - 1 themselves.  heads > 1 stays unbuilt.
 """
 import torch
 import torch.nn as nn
@@ -29,27 +32,56 @@ class Attention(nn.Module):
         self.dim_head = dim_head
         self.scale = dim_head ** -0.5
         self.to_qk = nn.Conv2d(dim, heads * dim_head * 2, 1, bias=False)
+        self.max_pos_size = max_pos_size
         self.pos_emb = RelPosEmb(max_pos_size, dim_head)
         self._packs = PackCache()
 
+    def _positional(self, fmap):
+        """None for the content attention, else whether the content logits take part (position_only wins over
+        position_and_content, modules.py:62-68).  Checks what must hold before anything is launched."""
+        if self.heads != 1:
+            raise NotImplementedError("only the single-head attention is on the AccFlow path")
+        if not (self.args.position_only or self.args.position_and_content):
+            return None
+        h, w = fmap.shape[-2:]
+        if h > self.max_pos_size or w > self.max_pos_size:
+            raise ValueError("positional attention: the %d x %d feature grid exceeds max_pos_size = %d" % (h, w, self.max_pos_size))
+        return not self.args.position_only
+
+    def _tables(self, qk):
+        emb = self.pos_emb
+        return ops.gma_pos_tables(qk, emb.rel_height.weight.detach().float().contiguous(),
+                                  emb.rel_width.weight.detach().float().contiguous(), self.dim_head, self.scale)
+
     @torch.no_grad()
-    @ops.range_guarded
     def forward(self, fmap):
-        """(B, dim, h, w) -> attn (B, heads=1, h*w, h*w) = softmax_j(scale * <q_i, k_j>)  (modules.py:54-76)"""
-        if self.heads != 1 or self.args.position_only or self.args.position_and_content:
-            raise NotImplementedError("only the single-head content attention is on the AccFlow path")
+        """(B, dim, h, w) -> attn (B, heads=1, h*w, h*w) = softmax_j(scale * <q_i, k_j>)  (modules.py:54-76); with
+        args.position_and_content the positional logits are added, with args.position_only they are the logits."""
+        content = self._positional(fmap)
         require_cuda(fmap)
-        qk = ops.conv2d(self._packs.conv("qk", self.to_qk), fmap.float())
-        return ops.gma_attention(qk, self.dim_head, self.scale)
+
+        def run():
+            qk = ops.conv2d(self._packs.conv("qk", self.to_qk), fmap.float())
+            if content is not None:
+                return ops.gma_attention_pos(qk, self._tables(qk), self.dim_head, self.scale, content)
+            return ops.gma_attention(qk, self.dim_head, self.scale)
+        return ops.with_range_guard(run, fmap.device, name="%s.forward" % type(self).__name__)
 
     @torch.no_grad()
     def forward_t(self, fmap, runs=None):
         """Same attention, transposed storage, for Aggregate's matrix-core path (internal to RAFTGMA).  In S16 mode the
-        matrix is stored pre-split (ops.gma_attention_s16): it is the aggregation GEMM's activation operand in all 12
-        refinement iterations and is then never converted again."""
+        matrix is stored pre-split (ops.gma_attention_s16 / ops.gma_attention_pos_s16): it is the aggregation GEMM's
+        activation operand in all 12 refinement iterations and is then never converted again."""
+        content = self._positional(fmap)
         require_cuda(fmap)
         qk = ops.conv2d(self._packs.conv("qk", self.to_qk), fmap.float())
-        if ops.s16_active() and self.dim_head % 32 == 0:
+        s16 = ops.s16_active() and self.dim_head % 32 == 0
+        if content is not None:
+            tab = self._tables(qk)
+            if s16:
+                return TransposedAttention(None, runs, attn16=ops.gma_attention_pos_s16(qk, tab, self.dim_head, self.scale, content))
+            return TransposedAttention(ops.gma_attention_pos_t(qk, tab, self.dim_head, self.scale, content), runs)
+        if s16:
             return TransposedAttention(None, runs, attn16=ops.gma_attention_s16(qk, self.dim_head, self.scale))
         return TransposedAttention(ops.gma_attention_t(qk, self.dim_head, self.scale), runs)
 

@@ -1786,6 +1786,75 @@ def gma_attention_s16(qk, D, scale):
     return attn16
 
 
+def gma_pos_tables(qk, rel_height, rel_width, D, scale):
+    """The positional logits of GMA's position_only / position_and_content attention as two tables per item: qk (B, 2D, H, W),
+    rel_height / rel_width the embedding weights (2 M - 1, D) -> tab (B, H + W, H*W) float32 with, for query pixel
+    i = (x, y), tab[b, u, i] = <scale q_i, rel_height[u - x + M - 1]> and tab[b, H + v, i] = <scale q_i, rel_width[v - y + M - 1]>
+    (accflow_gma_pos_tables_f32).  H or W above M raises ValueError before anything is launched."""
+    lib = _lib.load()
+    qk = _dense(qk, "qk")
+    rel_height, rel_width = _dense(rel_height, "rel_height"), _dense(rel_width, "rel_width")
+    B, C2, H, W = qk.shape
+    if (rel_height.dim() != 2 or rel_height.shape != rel_width.shape or rel_height.shape[1] != D or rel_height.shape[0] % 2 != 1
+            or C2 != 2 * D):
+        raise RuntimeError("gma_pos_tables: qk must be (B, 2 D, H, W) and the embeddings two (2 M - 1, D) tables")
+    M = (rel_height.shape[0] + 1) // 2
+    if H > M or W > M:
+        raise ValueError("gma_pos_tables: a %d x %d grid exceeds max_pos_size = %d" % (H, W, M))
+    tab = torch.empty((B, H + W, H * W), dtype=torch.float32, device=qk.device)
+    _check(lib.accflow_gma_pos_tables_f32(_p(qk), _p(rel_height), _p(rel_width), _p(tab), B, D, H, W, M, float(scale),
+                                          _stream()), "accflow_gma_pos_tables_f32")
+    return tab
+
+
+def _pos_args(qk, tab, D, name):
+    qk, tab = _dense(qk, "qk"), _dense(tab, "tab")
+    B, C2, H, W = qk.shape
+    if C2 != 2 * D or tuple(tab.shape) != (B, H + W, H * W):
+        raise RuntimeError("%s: qk must be (B, 2 D, H, W) and tab the (B, H + W, H*W) result of gma_pos_tables" % name)
+    return qk, tab, B, H, W
+
+
+def gma_attention_pos(qk, tab, D, scale, content):
+    """ops.gma_attention with the positional term of ops.gma_pos_tables: attn (B, 1, P, P) = softmax_j(content logits +
+    tab[u] + tab[H + v]); content=False (position_only): the positional logits alone."""
+    lib = _lib.load()
+    qk, tab, B, H, W = _pos_args(qk, tab, D, "gma_attention_pos")
+    P = H * W
+    attn = torch.empty((B, 1, P, P), dtype=torch.float32, device=qk.device)
+    _check(lib.accflow_gma_attention_pos_f32(_p(qk), _p(tab), _p(attn), int(bool(content)), B, D, H, W, float(scale), _stream()),
+           "accflow_gma_attention_pos_f32")
+    return attn
+
+
+def _gma_attention_pos_t(qk, tab, D, scale, content, s16):
+    lib = _lib.load()
+    qk, tab, B, H, W = _pos_args(qk, tab, D, "gma_attention_pos_s16" if s16 else "gma_attention_pos_t")
+    P = H * W
+    content = int(bool(content))
+    md = current_mode()
+    out = S16.empty(B, P, H, W, qk.device) if s16 else torch.empty((B, P, P), dtype=torch.float32, device=qk.device)
+    # (fp32 mode with content: no workspace - the scores then come from the fp32 GEMM)
+    nb = lib.accflow_gma_attention_pos_ws_bytes(D, H, W, content, int(s16)) if (s16 or not content or md != CONV_F32) else 0
+    ws = torch.empty(nb, dtype=torch.uint8, device=qk.device) if nb else None
+    _check(lib.accflow_gma_attention_pos_t(_p(qk), _p(tab), None if s16 else _p(out), ctypes.c_void_p(out.ptr()) if s16 else None,
+                                           _p(ws), md, content, B, D, H, W, float(scale), _stream()),
+           "accflow_gma_attention_pos_t")
+    return out
+
+
+def gma_attention_pos_t(qk, tab, D, scale, content):
+    """ops.gma_attention_t with the positional term: attnT (B, P, P), attnT[b, j, i] = attn[b, i, j]."""
+    return _gma_attention_pos_t(qk, tab, D, scale, content, False)
+
+
+def gma_attention_pos_s16(qk, tab, D, scale, content):
+    """ops.gma_attention_s16 with the positional term: the j-major attention pre-split (ops.S16 of P channels j over the
+    H x W pixels i), written by the softmax's normalising sweep; the fp32 scores exist for one item at a time, as workspace
+    (content=False: not at all - the product of the two normalised tables)."""
+    return _gma_attention_pos_t(qk, tab, D, scale, content, True)
+
+
 def gma_aggregate_s16(attn16_item, v, fmap0, fmap_bs, gamma, out0, out_bs, out16_0, out16_bs, n, D, H, W):
     """fmap + gamma * (attn @ v) for n items sharing one S16 attention; *_0 = data pointers of the first item's slices,
     *_bs the strides (4-byte words) to the next item's (accflow_gma_aggregate_s16)."""

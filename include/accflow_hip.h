@@ -604,6 +604,31 @@ long long accflow_gma_aggregate_ws_bytes(int B, int D, int P);
 int accflow_gma_aggregate_t_f32(const float* attnT, const float* v, const float* fmap, const float* gamma,
                                 float* out, long long out_bs, void* ws, int mode, int* guard, int B, int D, int H, int W,
                                 void* stream);
+/* GMA attention with relative position embeddings (gma/modules.py:6-31, 62-68: args.position_only and
+ * args.position_and_content; csrc/gma_pos.hip), heads = 1.  Query pixel i = (x, y), key pixel j = (u, v) of the H x W grid,
+ * q = scale * qk[:, :D], rel_height / rel_width the embedding weights (2 * max_pos - 1, D) as the state_dict holds them:
+ *   sim_pos[i][j] = A[i][u] + Bw[i][v],  A[i][u] = <q_i, rel_height[u - x + max_pos - 1]>,
+ *                                        Bw[i][v] = <q_i, rel_width[v - y + max_pos - 1]>.
+ * accflow_gma_pos_tables_f32 builds tab (B, H + W, H*W) fp32 once per image1: tab[b][u][i] = A[i][u] for the first H rows,
+ * tab[b][H + v][i] = Bw[i][v] for the next W (fp32 FMA on fp32 operands).  H > max_pos or W > max_pos returns 1.
+ * The attention entries take qk and tab; content = 1: softmax_j(scale * <q_i, k_j> + sim_pos[i][j]) (position_and_content,
+ * scores from the GEMMs of accflow_gma_attention_f32 / accflow_gma_attention_t_f32), content = 0: softmax_j(sim_pos[i][j])
+ * (position_only: no score matrix, no QK GEMM; qk is not read).
+ *   accflow_gma_attention_pos_f32: attn (B, P, P) row-major, what accflow_gma_attention_f32 returns.
+ *   accflow_gma_attention_pos_t:   exactly one of attnT (fp32 (B, P, P), j-major, what accflow_gma_attention_t_f32 returns)
+ *     and attn16 (the S16 tensor accflow_gma_attention_s16 returns, written by the normalising sweep itself) is non-NULL.
+ *     ws: accflow_gma_attention_pos_ws_bytes(D, H, W, content, s16 = attn16 != NULL) bytes - content = 1: the split GEMM's
+ *     workspace and, for the S16 output, the fp32 scores of ONE item (reused item after item); ws may be NULL for the fp32
+ *     output (then the scores come from the fp32 GEMM, as in mode ACCFLOW_CONV_F32).  content = 0: the softmax factorises,
+ *     softmax_j(A[u] + Bw[v]) = softmax_u(A) softmax_v(Bw) - ws holds the two normalised tables of ONE item ((H + W) H W
+ *     floats), the P x P pass is one multiply per element. */
+int accflow_gma_pos_tables_f32(const float* qk, const float* rel_height, const float* rel_width, float* tab, int B, int D,
+                               int H, int W, int max_pos, float scale, void* stream);
+int accflow_gma_attention_pos_f32(const float* qk, const float* tab, float* attn, int content, int B, int D, int H, int W,
+                                  float scale, void* stream);
+long long accflow_gma_attention_pos_ws_bytes(int D, int H, int W, int content, int s16);
+int accflow_gma_attention_pos_t(const float* qk, const float* tab, float* attnT, void* attn16, void* ws, int mode, int content,
+                                int B, int D, int H, int W, float scale, void* stream);
 
 /* ---- Backward of the fusion heads (the part of train_acc.py:113-312 that carries gradients - the estimator is
  * frozen, train_acc.py:164, and AccFlow_.py:172,182,195,198 detach flows / occlusion / error maps).  fp32 arithmetic.  The
