@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from accflow_amd import ops  # noqa: E402
+from accflow_amd import metrics, ops  # noqa: E402
 
 
 def preprocess(batch, device):
@@ -127,10 +127,11 @@ def main():
     alls, occs, viss = [], [], []
 
     def account(FN0, labels):
+        # calc_occ_mask + cal_epe as one launch pair (the mask is decided inside the reduction); float32 per-sample values
+        # as before, which is what gather_metrics exchanges
         bflows, fflows = labels
-        bmask, _ = calc_occ_mask(bflows[-1], fflows[-1])
-        e_all, e_occ, e_vis = cal_epe(FN0, bflows[-1], bmask)
-        alls.append(e_all), occs.append(e_occ), viss.append(e_vis)
+        m = metrics.cvo_metrics(FN0, bflows[-1], fflows[-1])
+        alls.append(m.epe.float()), occs.append(m.epe_occ.float()), viss.append(m.epe_vis.float())
 
     # batches are independent: the fusion chain of batch k runs underneath the estimator of batch k+1
     pipe = SequencePipeline(model) if a.acc == "acc" else None

@@ -1516,6 +1516,78 @@ def get_occ(flow, i1, i2, binary=True, out=None, out16=None):
     return out
 
 
+def _flow_shape(t, name, who, like=None, channels=2):
+    """Shape check of a (B, channels, H, W) operand BEFORE anything touches the library; `like`: the (B, H, W) it must match."""
+    if not (isinstance(t, torch.Tensor) and t.dim() == 4 and t.shape[1] == channels and t.numel() > 0):
+        raise RuntimeError("%s: %s must be a non-empty (B,%d,H,W) tensor, got %s" % (
+            who, name, channels, tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)))
+    bhw = (t.shape[0], t.shape[2], t.shape[3])
+    if like is not None and bhw != like:
+        raise RuntimeError("%s: %s is %s, expected (%d,%d,%d,%d)" % (who, name, tuple(t.shape), like[0], channels, like[1], like[2]))
+    return bhw
+
+
+def fb_occlusion(bflow, fflow, alpha=0.01, beta=0.5, want=("bw", "fw"), out_bw=None, out_fw=None):
+    """calc_occ_mask (test_cvo.py:53-78) in one launch: bflow = FN0 and fflow = F0N, both (B,2,H,W) -> (occ_bw, occ_fw), each
+    (B,1,H,W) of 0.0 / 1.0 with 1 = occluded: |flow + other(p + flow)| > alpha (|f| + |b|) + beta.  An entry not in `want` is
+    None and not computed; out_bw / out_fw: (B,1,H,W) tensors to write into (batch slices of a larger tensor are fine)."""
+    who = "fb_occlusion"
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in ("bw", "fw") for w in want):
+        raise RuntimeError("%s: want must name 'bw', 'fw' or both, got %r" % (who, want))
+    bhw = _flow_shape(bflow, "bflow", who)
+    _flow_shape(fflow, "fflow", who, like=bhw)
+    outs = []
+    for key, out in (("bw", out_bw), ("fw", out_fw)):
+        if key not in want:
+            if out is not None:
+                raise RuntimeError("%s: out_%s given but %r is not in want" % (who, key, key))
+        elif out is not None:
+            _flow_shape(out, "out_" + key, who, like=bhw, channels=1)
+        outs.append(out)
+    bbs, fbs = _plane4(bflow, "bflow"), _plane4(fflow, "fflow")
+    lib = _lib.load()
+    B, H, W = bhw
+    strides = []
+    for i, key in enumerate(("bw", "fw")):
+        if key in want and outs[i] is None:
+            outs[i] = torch.empty((B, 1, H, W), dtype=torch.float32, device=bflow.device)
+        strides.append(_plane4(outs[i], "out_" + key) if outs[i] is not None else 0)
+    _check(lib.accflow_fb_occlusion_f32(_p(bflow), bbs, _p(fflow), fbs, _p(outs[0]), strides[0], _p(outs[1]), strides[1],
+                                        float(alpha), float(beta), B, H, W, _stream()), "accflow_fb_occlusion_f32")
+    return outs[0], outs[1]
+
+
+def flow_metrics(pred, gt, mask=None, fflow=None, alpha=0.01, beta=0.5):
+    """Per-sample sums of pred against gt, both (B,2,H,W) -> (B,8) float64 on the device, epe = |pred - gt|:
+    [sum epe, sum epe*mask, sum mask, #(epe<1), #(epe<3), #(epe<5), sum |dx|+|dy|, pixels].  mask: (B,1,H,W) weights (cal_epe,
+    test_cvo.py:81-101); fflow: the CVO mode - gt is the backward flow and the mask is fb_occlusion(gt, fflow)[0], decided
+    inside the reduction; neither: columns 1 and 2 are 0.  Fixed-order reductions: a sample's row does not depend on the batch."""
+    who = "flow_metrics"
+    if mask is not None and fflow is not None:
+        raise RuntimeError("%s: pass mask or fflow, not both" % who)
+    bhw = _flow_shape(pred, "pred", who)
+    _flow_shape(gt, "gt", who, like=bhw)
+    if mask is not None:
+        _flow_shape(mask, "mask", who, like=bhw, channels=1)
+    if fflow is not None:
+        _flow_shape(fflow, "fflow", who, like=bhw)
+    pbs, gbs = _plane4(pred, "pred"), _plane4(gt, "gt")
+    mbs = _plane4(mask, "mask") if mask is not None else 0
+    fbs = _plane4(fflow, "fflow") if fflow is not None else 0
+    lib = _lib.load()
+    B, H, W = bhw
+    nbytes = lib.accflow_flow_metrics_ws_bytes(B, H, W)
+    if nbytes <= 0:
+        raise RuntimeError("%s: unsupported size B=%d H=%d W=%d" % (who, B, H, W))
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=pred.device)
+    sums = torch.empty((B, 8), dtype=torch.float64, device=pred.device)
+    mode = 1 if mask is not None else (2 if fflow is not None else 0)
+    _check(lib.accflow_flow_metrics_f32(_p(pred), pbs, _p(gt), gbs, _p(mask), mbs, _p(fflow), fbs, mode, float(alpha), float(beta),
+                                        _p(sums), _p(ws), B, H, W, _stream()), "accflow_flow_metrics_f32")
+    return sums
+
+
 def downflow8(flow):
     lib = _lib.load()
     _plane4(flow, "flow")

@@ -111,8 +111,10 @@ def add_noise(images):
 
 def validate(model, loader, dev, limit):
     """train_acc.py:253-271 on this rank: mean of sequence_loss_acc's metrics over the validation batches."""
+    from accflow_amd import metrics
     from accflow_amd.eval_cvo import preprocess
-    mets, last = [], None
+    keys = ("epe", "1px", "3px", "5px", "loss")
+    total, n, last = None, 0, None
     with torch.no_grad():
         for i, batch in enumerate(loader):
             if limit is not None and i >= limit:
@@ -120,13 +122,18 @@ def validate(model, loader, dev, limit):
             d = preprocess(batch, dev)
             out = model(d["imgs"])
             gts = d["bflows"][:len(out)]
-            m = sequence_loss_metrics(out, gts)
-            m["loss"] = sum(float((o - g).abs().mean()) for o, g in zip(out, gts))
-            mets.append(m)
+            # one reduction per output, everything stays on the device: the samples of a batch have the same pixel count, so
+            # the mean of the per-sample means is the batch mean sequence_loss_metrics takes
+            per = [metrics.flow_metrics(o, g) for o, g in zip(out, gts)]
+            fin = per[-1]
+            row = torch.stack([fin.epe.mean(), fin.px1.mean(), fin.px3.mean(), fin.px5.mean(), sum(p.l1.mean() for p in per)])
+            total = row if total is None else total + row
+            n += 1
             last = out[-1]
-    if not mets:
+    if not n:
         raise RuntimeError("validate: the validation loader yielded no batch")
-    return {"val_" + k: sum(m[k] for m in mets) / len(mets) for k in mets[0]}, last
+    vals = (total / n).cpu().tolist()          # the one transfer of the validation
+    return {"val_" + k: v for k, v in zip(keys, vals)}, last
 
 
 def main(argv=None):

@@ -430,6 +430,33 @@ int accflow_upflow8_f32(const float* flow, long long flow_bs, float* out, long l
 /* forward_interpolate (raft/utils/utils.py:31-63): nearest kept source of the flow pushed along itself; flow, out (B,2,H8,W8), not overlapping. */
 int accflow_forward_interpolate_f32(const float* flow, float* out, int B, int H8, int W8, void* stream);
 
+/* ---- Judging a flow: forward-backward occlusion masks and metric sums (test_cvo.py:53-101, loss.py:37-45) ----
+ * Flows are (B,2,H,W), masks (B,1,H,W), all fp32 with dense channel blocks and the batch strides given.  No float atomics:
+ * every result is reproducible bit for bit.
+ *
+ * calc_occ_mask (test_cvo.py:53-78) in one launch.  With f = fflow[p], b = bflow[p] and thr = alpha (|f| + |b|) + beta (L2
+ * norms: the reference's `length_sq` is the norm),
+ *     occ_fw[p] = |f + bilinear_zeros(bflow, p + f)| > thr,      occ_bw[p] = |b + bilinear_zeros(fflow, p + b)| > thr,
+ * stored as 0.0f / 1.0f, 1 = occluded.  Either output may be NULL (not both) and is then not computed.  Sampling follows
+ * accflow_backwarp_f32: coordinates clamped to +-1e6, corners outside the plane read element 0 with weight 0 - a non-finite
+ * flow never forms an out-of-plane address; its comparison decides the pixel, and a NaN compares false (0). */
+int accflow_fb_occlusion_f32(const float* bflow, long long b_bs, const float* fflow, long long f_bs, float* occ_bw,
+                             long long obw_bs, float* occ_fw, long long ofw_bs, float alpha, float beta, int B, int H, int W,
+                             void* stream);
+
+/* Per-sample sums of pred against gt, sums (B,8) DOUBLE with epe = sqrt(dx^2 + dy^2), d = pred - gt:
+ *     0: sum epe   1: sum epe*mask   2: sum mask   3: #(epe<1)   4: #(epe<3)   5: #(epe<5)   6: sum |dx|+|dy|   7: pixels
+ * mode 0: no mask (columns 1, 2 are 0);  mode 1: `mask` (any values) is the weight, as cal_epe uses it (test_cvo.py:81-101);
+ * mode 2: the mask is occ_bw of (gt = bflow, fflow, alpha, beta) as above, decided on the fly - nothing is stored for it.
+ * Pointers a mode does not use may be NULL.  Two fixed-order stages: a workgroup reduces a fixed run of pixels of one sample
+ * to an 8-float partial in `ws` (accflow_flow_metrics_ws_bytes(B,H,W) bytes; the run length is a constant), then one wave
+ * per sample adds that sample's partials in index order in double.  A sample's row therefore has the same bits whatever B
+ * is and wherever in the batch it sits.  B <= 65535.  The size query returns 0 for invalid sizes. */
+long long accflow_flow_metrics_ws_bytes(int B, int H, int W);
+int accflow_flow_metrics_f32(const float* pred, long long p_bs, const float* gt, long long g_bs, const float* mask,
+                             long long m_bs, const float* fflow, long long f_bs, int mode, float alpha, float beta,
+                             double* sums, float* ws, int B, int H, int W, void* stream);
+
 /* InstanceNorm2d (no affine, eps, biased var; extractor.py:36-39) over each (b,c) plane of `x`,
  * fused with what follows it in ResidualBlock.forward (extractor.py:56-63):
  *   mode 0: out = norm(x)                    (downsample branch)
