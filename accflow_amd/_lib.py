@@ -133,6 +133,9 @@ SIGNATURES = {
     "accflow_flow_metrics_ws_bytes": [c_i, c_i, c_i],
     "accflow_flow_metrics_f32": [c_f, c_ll, c_f, c_ll, c_f, c_ll, c_f, c_ll, c_i, ctypes.c_float, ctypes.c_float, c_f, c_f, c_i, c_i,
                                  c_i, c_f],
+    "accflow_flow_maxrad_ws_bytes": [c_i, c_i, c_i],
+    "accflow_flow_maxrad_f32": [c_f, c_ll, ctypes.c_float, c_i, c_f, c_f, c_i, c_i, c_i, c_f],
+    "accflow_flow_to_rgb_u8": [c_f, c_ll, c_f, ctypes.c_float, c_f, c_ll, c_i, c_i, c_i, c_i, c_i, c_f],
     "accflow_instance_norm_f32": [c_f, c_f, c_f, c_i, c_i, c_i, ctypes.c_float, c_i, c_f],
     "accflow_split_tanh_relu_f32": [c_f, c_f, c_ll, c_f, c_ll, c_i, c_i, c_i, c_i, c_f],
     "accflow_split_tanh_relu_idx_f32": [c_f, c_i, ctypes.POINTER(c_i), c_f, c_ll, c_f, c_ll, c_i, c_i, c_i, c_i, c_f],
@@ -180,7 +183,7 @@ RETURNS_LONGLONG = frozenset((
     "accflow_gma_aggregate_ws_bytes", "accflow_gma_attention_ws_bytes", "accflow_gma_aggregate_s16_ws_bytes",
     "accflow_gma_attention_s16_ws_bytes", "accflow_gma_attention_alt_ws_bytes", "accflow_gma_aggregate_alt_ws_bytes",
     "accflow_corr_disp_level_elems", "accflow_corr_alt_pyramid_elems", "accflow_s16_item_words",
-    "accflow_gma_attention_pos_ws_bytes", "accflow_flow_metrics_ws_bytes",
+    "accflow_gma_attention_pos_ws_bytes", "accflow_flow_metrics_ws_bytes", "accflow_flow_maxrad_ws_bytes",
 ))
 
 _lock = threading.Lock()

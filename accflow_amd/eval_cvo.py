@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from accflow_amd import metrics, ops  # noqa: E402
+from accflow_amd import metrics, ops, viz  # noqa: E402
 
 
 def preprocess(batch, device):
@@ -112,6 +112,8 @@ def main():
     ap.add_argument("--batch", type=int, default=10)   # test_cvo.py:114
     ap.add_argument("--result-dir", type=str, default=".",
                     help="where test_result_<split>_E6.txt is appended (test_cvo.py:163-165 writes to the working directory)")
+    ap.add_argument("--viz", type=str, default=None, metavar="DIR",
+                    help="write DIR/<batch index>.png: the predicted final flow of each batch's sample 0, colour coded")
     a = ap.parse_args()
     import torch.distributed as dist
     from accflow_amd.data.dataset import fetch_valid_dataloader
@@ -125,13 +127,18 @@ def main():
     model = build_model(a.acc, a.ofe, a.acc_ckpt, a.ofe_ckpt, dev)
     loader, _ = fetch_valid_dataloader(keys=["fflows", "bflows"], split=a.data, batch=a.batch)
     alls, occs, viss = [], [], []
+    if a.viz:
+        os.makedirs(a.viz, exist_ok=True)
 
     def account(FN0, labels):
         # calc_occ_mask + cal_epe as one launch pair (the mask is decided inside the reduction); float32 per-sample values
         # as before, which is what gather_metrics exchanges
-        bflows, fflows = labels
+        bflows, fflows, index = labels
         m = metrics.cvo_metrics(FN0, bflows[-1], fflows[-1])
         alls.append(m.epe.float()), occs.append(m.epe_occ.float()), viss.append(m.epe_vis.float())
+        if a.viz:
+            # (every rank holds its own block of the batch: its sample 0 is another sample)
+            viz.save_flow(FN0, os.path.join(a.viz, "%06d.png" % index if world == 1 else "%06d_rank%d.png" % (index, rank)))
 
     # batches are independent: the fusion chain of batch k runs underneath the estimator of batch k+1
     pipe = SequencePipeline(model) if a.acc == "acc" else None
@@ -146,9 +153,9 @@ def main():
         imgs, bflows, fflows = d["imgs"][:end + 1], d["bflows"][:end - 1], d["fflows"][:end - 1]
         with torch.no_grad():
             if pipe is None:
-                account(model(imgs[-1], imgs[0]), (bflows, fflows))
+                account(model(imgs[-1], imgs[0]), (bflows, fflows, index))
                 continue
-            in_flight.append((bflows, fflows))
+            in_flight.append((bflows, fflows, index))
             outs = pipe.submit(imgs)
         if outs:   # (None: nothing harvested yet; []: a sequence of fewer than 3 frames has no accumulated flow)
             account(outs[-1], in_flight.pop(0))

@@ -1588,6 +1588,70 @@ def flow_metrics(pred, gt, mask=None, fflow=None, alpha=0.01, beta=0.5):
     return sums
 
 
+def _viz_clip(clip, who):
+    """clip_flow as the C entries take it: None -> -1 (no clip), otherwise a float >= 0."""
+    if clip is None:
+        return -1.0
+    clip = float(clip)
+    if not clip >= 0.0:
+        raise RuntimeError("%s: clip must be >= 0 or None, got %r" % (who, clip))
+    return clip
+
+
+def flow_maxrad(flow, clip=None, shared=False):
+    """The colour coding's scale: flow (B,2,H,W) -> (B,) float32 on the device, the largest sqrt(u^2 + v^2) of each sample
+    (bit-equal to numpy's float32; pixels with a non-finite component or one beyond 1e9 are skipped, a sample without a valid
+    pixel gives 0).  shared: the maximum over the whole batch in every entry.  clip: np.clip(flow, 0, clip) first."""
+    who = "flow_maxrad"
+    clip = _viz_clip(clip, who)
+    B, H, W = _flow_shape(flow, "flow", who)
+    fbs = _plane4(flow, "flow")
+    lib = _lib.load()
+    nbytes = lib.accflow_flow_maxrad_ws_bytes(B, H, W)
+    if nbytes <= 0:
+        raise RuntimeError("%s: unsupported size B=%d H=%d W=%d" % (who, B, H, W))
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=flow.device)
+    maxrad = torch.empty(B, dtype=torch.float32, device=flow.device)
+    _check(lib.accflow_flow_maxrad_f32(_p(flow), fbs, clip, int(bool(shared)), _p(maxrad), _p(ws), B, H, W, _stream()),
+           "accflow_flow_maxrad_f32")
+    return maxrad
+
+
+def flow_to_rgb(flow, maxrad, clip=None, bgr=False, layout="hwc", out=None):
+    """The Middlebury colour coding of flow (B,2,H,W) at the scales maxrad (B,) float32 on the device -> uint8 (B,H,W,3)
+    (layout "hwc") or (B,3,H,W) ("chw"), RGB or BGR.  out: a uint8 tensor of that shape to write into; its samples must be
+    dense, the batch stride is free ("chw": a multiple of 4 bytes from a 4-byte aligned base)."""
+    who = "flow_to_rgb"
+    clip = _viz_clip(clip, who)
+    if layout not in ("hwc", "chw"):
+        raise RuntimeError("%s: layout must be 'hwc' or 'chw', got %r" % (who, layout))
+    B, H, W = _flow_shape(flow, "flow", who)
+    shape = (B, H, W, 3) if layout == "hwc" else (B, 3, H, W)
+    if not (isinstance(maxrad, torch.Tensor) and maxrad.dtype == torch.float32 and tuple(maxrad.shape) == (B,)
+            and maxrad.is_contiguous()):
+        raise RuntimeError("%s: maxrad must be a contiguous float32 tensor of shape (%d,)" % (who, B))
+    if out is not None:
+        if not (isinstance(out, torch.Tensor) and out.dtype == torch.uint8 and tuple(out.shape) == shape):
+            raise RuntimeError("%s: out must be a uint8 tensor of shape %s" % (who, shape))
+        if not out[0].is_contiguous():
+            raise RuntimeError("%s: every sample of out must be dense (strides %s)" % (who, out.stride()))
+    fbs = _plane4(flow, "flow")
+    if not maxrad.is_cuda or (out is not None and not out.is_cuda):
+        raise RuntimeError("%s: expected CUDA tensors for maxrad and out" % who)
+    lib = _lib.load()
+    if out is None:
+        # (planar samples start on a dword: the batch stride is 3 H W rounded up to 4, the result a view when that differs)
+        n = 3 * H * W
+        pitch = n if layout == "hwc" else (n + 3) // 4 * 4
+        out = torch.empty((B, pitch), dtype=torch.uint8, device=flow.device)[:, :n].view(shape)
+    obs = out.stride(0) if B > 1 else 3 * H * W
+    if layout == "chw" and (out.data_ptr() % 4 or (B > 1 and obs % 4)):
+        raise RuntimeError("%s: a 'chw' output needs a 4-byte aligned base and batch stride" % who)
+    _check(lib.accflow_flow_to_rgb_u8(_p(flow), fbs, _p(maxrad), clip, _p(out), obs, int(layout == "chw"), int(bool(bgr)), B, H, W,
+                                      _stream()), "accflow_flow_to_rgb_u8")
+    return out
+
+
 def downflow8(flow):
     lib = _lib.load()
     _plane4(flow, "flow")

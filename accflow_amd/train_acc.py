@@ -45,7 +45,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 DEFAULTS = dict(epochs=60, lr=1.2e-4, wdecay=1e-5, epsilon=1e-8, batch_per_gpu=6, clip=1.0, add_noise=True, log_freq=100,
-                valid_freq=1000, image_size=[256, 256], flow_pretrained=None, valid_sample=500, gpus=[0], loss_type="L1")
+                valid_freq=1000, image_size=[256, 256], flow_pretrained=None, valid_sample=500, gpus=[0], loss_type="L1",
+                visual_samples=[])
 
 
 def parse_options(path):
@@ -109,8 +110,10 @@ def add_noise(images):
     return [x + noise for x in images]
 
 
-def validate(model, loader, dev, limit):
-    """train_acc.py:253-271 on this rank: mean of sequence_loss_acc's metrics over the validation batches."""
+def validate(model, loader, dev, limit, keep=None):
+    """train_acc.py:253-271 on this rank: mean of sequence_loss_acc's metrics over the validation batches.
+    keep: a dict that receives {batch index: sample 0 of that batch's last output, (1,2,H,W) on the device} for the batch
+    indices it already has as keys (train_acc.py:266's val_result, restricted to `visual_samples`)."""
     from accflow_amd import metrics
     from accflow_amd.eval_cvo import preprocess
     keys = ("epe", "1px", "3px", "5px", "loss")
@@ -130,10 +133,23 @@ def validate(model, loader, dev, limit):
             total = row if total is None else total + row
             n += 1
             last = out[-1]
+            if keep is not None and i in keep:
+                keep[i] = last[:1].clone()
     if not n:
         raise RuntimeError("validate: the validation loader yielded no batch")
     vals = (total / n).cpu().tolist()          # the one transfer of the validation
     return {"val_" + k: v for k, v in zip(keys, vals)}, last
+
+
+def save_visual_samples(kept, log_dir, step):
+    """train_acc.py:283-289: <log_dir>/val/im<index>/<step>.png for every kept validation sample, coloured on the device."""
+    from accflow_amd import viz
+    for index, flow in sorted(kept.items()):
+        if flow is None:          # (the validation had fewer batches than this index)
+            continue
+        save_dir = os.path.join(log_dir, "val", "im%03d" % index)
+        os.makedirs(save_dir, exist_ok=True)
+        viz.save_flow(flow, os.path.join(save_dir, "%06d.png" % step))
 
 
 def main(argv=None):
@@ -260,7 +276,8 @@ def main(argv=None):
             last = (a.steps is not None and step >= a.steps) or step >= num_steps
             if step % args.valid_freq == 0 or last:
                 if rank == 0:
-                    vm, _ = validate(model, vloader, dev, a.valid_batches)
+                    kept = {int(i): None for i in args.visual_samples}
+                    vm, _ = validate(model, vloader, dev, a.valid_batches, keep=kept)
                     if vm["val_epe"] <= best_epe:
                         best_epe, best_step, new_best = vm["val_epe"], step, True
                     else:
@@ -268,6 +285,7 @@ def main(argv=None):
                     extra = {"best_epe": best_epe, "best_step": best_step, "synthetic": bool(synthetic_used)}
                     save_ckpt(step, scheduler, optimizer, model, ckpt_dir, True, extra)
                     if new_best:
+                        save_visual_samples(kept, log_dir, step)
                         save_ckpt(step, scheduler, optimizer, model, ckpt_dir, False, extra)
                         rotate_ckpts(ckpt_dir)
                     log.info("Validation EPE: %.3f, current best EPE: %.3f(step: %s)", vm["val_epe"], best_epe, best_step)

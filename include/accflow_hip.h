@@ -457,6 +457,33 @@ int accflow_flow_metrics_f32(const float* pred, long long p_bs, const float* gt,
                              long long m_bs, const float* fflow, long long f_bs, int mode, float alpha, float beta,
                              double* sums, float* ws, int B, int H, int W, void* stream);
 
+/* ---- Showing a flow: the Middlebury colour coding (Baker et al., ICCV 2007; the reference's utils/flow_viz.py) ----
+ * flow is (B,2,H,W) fp32 with dense channel blocks and the batch stride given (in elements).  With the scale s of a sample,
+ *     (u, v) = flow / (s + 1e-5),   rad = |(u, v)|,   fk = (atan2(-v, -u) / pi + 1) / 2 * 54,   k0 = floor(fk),   f = fk - k0,
+ *     col = wheel[k0] + f (wheel[(k0 + 1) mod 55] - wheel[k0]),   col = rad <= 1 ? 1 - rad (1 - col) : 0.75 col,
+ * the pixel is floor(255 col) per channel; the wheel's 55 entries (RY 15, YG 6, GC 4, CB 11, BM 13, MR 6) are a table of
+ * the unit.  `clip` >= 0 applies numpy's clip(flow, 0, clip) to both components first (negative components become 0, as in
+ * the reference; -0.0 and NaN pass through); clip < 0: none.  A pixel with a component that is then NaN, +-inf or beyond
+ * 1e9 in magnitude (Middlebury's "unknown") takes no part in the scale and is painted black.
+ *
+ * The scale: maxrad[b] = max over the valid pixels of sqrtf(u*u + v*v), each operation rounded on its own (bit-equal to
+ * numpy's float32), 0 for a sample without a valid pixel; shared != 0: the maximum over the whole batch, written to all B
+ * entries.  Two fixed-order stages without atomics: a workgroup reduces a constant run of pixels of one sample into `ws`
+ * (accflow_flow_maxrad_ws_bytes(B,H,W) bytes), one wave finishes a sample - a sample's scale does not depend on the batch.
+ * B <= 65535, H W < 2^31 / 3; the size query returns 0 for sizes the entries refuse. */
+long long accflow_flow_maxrad_ws_bytes(int B, int H, int W);
+int accflow_flow_maxrad_f32(const float* flow, long long f_bs, float clip, int shared, float* maxrad, float* ws, int B, int H,
+                            int W, void* stream);
+
+/* The picture.  maxrad: (B,) scales in DEVICE memory - from the entry above or any other source; a scale below a sample's
+ * true maximum sends the pixels beyond it into the 0.75 col branch.  out: uint8, sample b at out + b * o_bs BYTES;
+ * planar == 0: (H,W,3) packed, any byte address and stride (a sample of 3 H W bytes need not start on a dword);
+ * planar != 0: (3,H,W), `out` and o_bs multiples of 4.  bgr != 0 swaps the first and the third channel.  A thread paints 4
+ * consecutive pixels and stores them as 3 aligned dwords; the up to 3 pixels in front of a packed sample's first aligned
+ * group and behind its last one, and a plane that starts off a dword boundary, are stored as bytes. */
+int accflow_flow_to_rgb_u8(const float* flow, long long f_bs, const float* maxrad, float clip, unsigned char* out,
+                           long long o_bs, int planar, int bgr, int B, int H, int W, void* stream);
+
 /* InstanceNorm2d (no affine, eps, biased var; extractor.py:36-39) over each (b,c) plane of `x`,
  * fused with what follows it in ResidualBlock.forward (extractor.py:56-63):
  *   mode 0: out = norm(x)                    (downsample branch)
