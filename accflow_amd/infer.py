@@ -1,0 +1,121 @@
+#!/usr/bin/env python3
+"""Long-range flow of a folder of frames: python -m accflow_amd.infer --frames DIR|GLOB --out DIR [--flo] [--kitti] [--png]
+
+The frames (PNG or binary PPM, all of one size, in sorted order) are decoded into one pinned buffer, sent to the device with
+one copy and turned into the estimators' input with one launch (frames.FramePadder.ingest).  They are then pushed frame by
+frame through AccFlowStream (--acc acc; constant memory whatever the length) or, with --acc direct, the estimator runs on
+(frame i, frame 0) for every i.  For each i >= 2 the flow F(i -> 0) is written as
+    flow_<i>_to_0.flo        --flo    Middlebury .flo, float32
+    flow_<i>_to_0_kitti.png  --kitti  16-bit PNG, KITTI's coding: 64 f + 32768, third channel 1 = valid
+    flow_<i>_to_0.png        --png    the Middlebury colour coding
+from ops.flow_export and viz.flow_to_image; nothing but the file's bytes is formed on the host.
+
+The colour PNGs of a run share a scale so that their colours are comparable: picture i is drawn at the largest |flow| of the
+PADDED flows 2..i - what has been seen so far, not the whole sequence's maximum, which a stream cannot know.  A flow that
+grows along the sequence therefore keeps its colours from its frame on; earlier pictures are not redrawn.
+
+Without checkpoints the deterministic synthetic weights are used (announced on stderr): the files are then good for timing
+and for testing the pipeline, not for looking at.
+"""
+import argparse
+import glob
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from accflow_amd import frames as _frames, ops, viz  # noqa: E402
+
+EXTENSIONS = (".png", ".ppm")
+KITTI_SCALE = 64.0
+
+
+def frame_paths(spec):
+    """DIR: its .png / .ppm files; anything else: a glob pattern.  Sorted by name."""
+    if os.path.isdir(spec):
+        paths = [os.path.join(spec, n) for n in os.listdir(spec) if n.lower().endswith(EXTENSIONS)]
+    else:
+        paths = glob.glob(spec)
+    return sorted(paths)
+
+
+def run(frames, out=None, acc="acc", ofe="raft", acc_ckpt=None, ofe_ckpt=None, iters=None, pad="sintel", flo=False, kitti=False,
+        png=False, bgr=False, model=None, device="cuda"):
+    """frames: a directory, a glob pattern or a list of paths.  Returns [F(i -> 0) for i = 2 .. n-1], each (1,2,H,W) float32
+    on the device at the frames' own size (a view of the padded flow).  out: the directory the files go to (needed with flo,
+    kitti or png).  model: a built model to use instead of eval_cvo.build_model(acc, ofe, acc_ckpt, ofe_ckpt, device)."""
+    from accflow_amd.networks.AccFlow_ import AccFlowStream
+    paths = frame_paths(frames) if isinstance(frames, str) else list(frames)
+    if len(paths) < 3:
+        raise ValueError("infer: %d frame(s) found, an accumulated flow needs at least 3" % len(paths))
+    if (flo or kitti or png) and out is None:
+        raise ValueError("infer: an output directory is needed to write files")
+    if acc not in ("acc", "direct") or pad not in ("sintel", "kitti"):
+        raise ValueError("infer: acc is 'acc' or 'direct' and pad 'sintel' or 'kitti', got %r and %r" % (acc, pad))
+    device = torch.device(device)
+    if model is None:
+        from accflow_amd.eval_cvo import build_model
+        if not (acc_ckpt if acc == "acc" else ofe_ckpt):
+            print("infer: no checkpoint given - running on the deterministic synthetic weights", file=sys.stderr)
+        model = build_model(acc, ofe, acc_ckpt, ofe_ckpt, device)
+    if out is not None:
+        os.makedirs(out, exist_ok=True)
+    u8 = _frames.load_frames(paths, device)
+    padder = _frames.FramePadder(u8.shape[1:3], mode=pad)
+    x = padder.ingest(u8, layout="hwc", bgr=bgr)
+    kw = {} if iters is None else {"iters": iters}
+    stream = AccFlowStream(model, **kw) if acc == "acc" else None
+    flows, seen = [], None
+    with torch.no_grad():
+        for i in range(len(paths)):
+            if stream is not None:
+                got = stream.push(x[i:i + 1])
+            else:
+                got = [model(x[i:i + 1], x[0:1], **kw)] if i >= 2 else []
+            for flow in got:
+                flow = flow.contiguous()
+                flows.append(padder.unpad(flow))
+                stem = os.path.join(out, "flow_%d_to_0" % i) if out is not None else None
+                if flo:
+                    _frames.write_flo(stem + ".flo", padder.export(flow, coding="f32")[0])
+                if kitti:
+                    _frames.write_png16(stem + "_kitti.png", padder.export(flow, coding="u16", scale=KITTI_SCALE, big_endian=True)[0])
+                if png:
+                    rad = ops.flow_maxrad(flow)
+                    seen = rad if seen is None else torch.maximum(seen, rad)
+                    y0, x0, H, W = padder.crop
+                    viz.write_png(stem + ".png", viz.flow_to_image(flow, max_rad=seen)[0, y0:y0 + H, x0:x0 + W])
+    return flows
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--frames", required=True, metavar="DIR|GLOB")
+    ap.add_argument("--out", required=True, metavar="DIR")
+    ap.add_argument("--acc", "-acc", choices=["acc", "direct"], default="acc")
+    ap.add_argument("--ofe", "-ofe", choices=["raft", "gma"], default="raft")
+    ap.add_argument("--acc_ckpt", default=None)
+    ap.add_argument("--ofe_ckpt", default=None)
+    ap.add_argument("--iters", type=int, default=None, help="the estimator's refinement iterations (default: the model's)")
+    ap.add_argument("--pad", choices=["sintel", "kitti"], default="sintel")
+    ap.add_argument("--flo", action="store_true", help="write Middlebury .flo files")
+    ap.add_argument("--kitti", action="store_true", help="write 16-bit KITTI flow PNGs")
+    ap.add_argument("--png", action="store_true", help="write colour-coded PNGs")
+    ap.add_argument("--bgr", action="store_true", help="hand the model BGR channel order (weights trained on BGR-decoded frames)")
+    a = ap.parse_args(argv)
+    if not (a.flo or a.kitti or a.png):
+        a.flo = True
+    dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", 0)))
+    torch.cuda.set_device(dev)
+    flows = run(a.frames, a.out, acc=a.acc, ofe=a.ofe, acc_ckpt=a.acc_ckpt, ofe_ckpt=a.ofe_ckpt, iters=a.iters, pad=a.pad,
+                flo=a.flo, kitti=a.kitti, png=a.png, bgr=a.bgr, device=dev)
+    print("infer: %d flow(s) of %d x %d written to %s" % (len(flows), flows[0].shape[2], flows[0].shape[3], a.out))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

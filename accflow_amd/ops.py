@@ -1652,6 +1652,94 @@ def flow_to_rgb(flow, maxrad, clip=None, bgr=False, layout="hwc", out=None):
     return out
 
 
+def frames_from_u8(src, layout="hwc", bgr=False, pad=(0, 0, 0, 0), normalize=True, out=None):
+    """8-bit frames -> the estimators' input in one launch: src uint8 (N,H,W,3) (layout "hwc") or (N,3,H,W) ("chw"), RGB or
+    BGR -> float32 (N,3,H+t+b,W+l+r), pad = (l, r, t, b) replicated as F.pad(..., mode="replicate") does it.  normalize:
+    2 * (x / 255.0) - 1 with torch's bits; otherwise the plain values 0..255.  src is taken as it is, with its byte strides:
+    a pitched or sliced view (rows, planes and samples at any distance, any base address) is not made contiguous - only the
+    bytes of a row must be adjacent.  out: a float32 tensor of the result's shape with dense samples to write into."""
+    who = "frames_from_u8"
+    if layout not in ("hwc", "chw"):
+        raise RuntimeError("%s: layout must be 'hwc' or 'chw', got %r" % (who, layout))
+    cdim = 3 if layout == "hwc" else 1
+    if not (isinstance(src, torch.Tensor) and src.dim() == 4 and src.shape[cdim] == 3 and src.numel() > 0):
+        raise RuntimeError("%s: src must be a non-empty %s tensor, got %s" % (
+            who, "(N,H,W,3)" if layout == "hwc" else "(N,3,H,W)", tuple(src.shape) if isinstance(src, torch.Tensor) else type(src)))
+    if src.dtype != torch.uint8:
+        raise RuntimeError("%s: src must be uint8, got %s" % (who, src.dtype))
+    try:
+        pads = tuple(int(p) for p in pad)
+        exact = all(p == q for p, q in zip(pads, pad))
+    except (TypeError, ValueError):
+        pads, exact = (), False
+    if len(pads) != 4 or not exact or min(pads) < 0:
+        raise RuntimeError("%s: pad must be four non-negative integers (left, right, top, bottom), got %r" % (who, pad))
+    st = src.stride()
+    if layout == "hwc":
+        N, H, W = src.shape[0], src.shape[1], src.shape[2]
+        ok, s_row, s_plane = st[3] == 1 and (W == 1 or st[2] == 3), st[1], 0
+    else:
+        N, H, W = src.shape[0], src.shape[2], src.shape[3]
+        ok, s_row, s_plane = W == 1 or st[3] == 1, st[2], st[1]
+    if not ok:
+        raise RuntimeError("%s: the bytes of a row of src must be adjacent (strides %s)" % (who, st))
+    shape = (N, 3, H + pads[2] + pads[3], W + pads[0] + pads[1])
+    if out is not None and not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and tuple(out.shape) == shape):
+        raise RuntimeError("%s: out must be a float32 tensor of shape %s" % (who, shape))
+    if not src.is_cuda:
+        raise RuntimeError("%s: expected CUDA tensors" % who)
+    obs = _plane4(out, "out") if out is not None else 3 * shape[2] * shape[3]
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=src.device)
+    _check(lib.accflow_frames_from_u8(_p(src), st[0] if N > 1 else 0, s_row if H > 1 else 0, s_plane, int(layout == "chw"),
+                                      int(bool(bgr)), int(bool(normalize)), _p(out), obs, N, H, W, pads[0], pads[1], pads[2],
+                                      pads[3], _stream()), "accflow_frames_from_u8")
+    return out
+
+
+def flow_export(flow, crop=None, coding="f32", scale=64.0, big_endian=False, out=None):
+    """A flow as the payload of a flow file, in one launch: flow (N,2,Hp,Wp), crop = (y0, x0, H, W) (None: everything; `unpad`
+    as arithmetic, nothing is copied first) ->
+      coding "f32": float32 (N,H,W,2), (u, v) interleaved - a Middlebury .flo file's payload (frames.write_flo);
+      coding "u16": uint16 (N,H,W,3) = (code(u), code(v), valid), code(f) = trunc(clip(scale * f + 32768, 0, 65535)) in fp32;
+                    a NaN or infinite component has code 0 and makes valid 0.  scale 64: KITTI, 128: CVO.  big_endian: every
+                    sample byte-swapped - the scanlines of a 16-bit PNG (frames.write_png16).
+    out: a tensor of that shape and dtype (torch.int16 is taken for uint16) with dense samples to write into."""
+    who = "flow_export"
+    if coding not in ("f32", "u16"):
+        raise RuntimeError("%s: coding must be 'f32' or 'u16', got %r" % (who, coding))
+    N, Hp, Wp = _flow_shape(flow, "flow", who)
+    if crop is None:
+        crop = (0, 0, Hp, Wp)
+    try:
+        y0, x0, H, W = (int(c) for c in crop)
+    except (TypeError, ValueError):
+        raise RuntimeError("%s: crop must be (y0, x0, H, W), got %r" % (who, crop))
+    if not (y0 >= 0 and x0 >= 0 and H > 0 and W > 0 and y0 + H <= Hp and x0 + W <= Wp):
+        raise RuntimeError("%s: crop %r does not lie inside the %d x %d flow" % (who, tuple(crop), Hp, Wp))
+    scale = float(scale)
+    if coding == "u16" and not (scale > 0.0 and scale < float("inf")):
+        raise RuntimeError("%s: scale must be a positive finite number, got %r" % (who, scale))
+    shape = (N, H, W, 2) if coding == "f32" else (N, H, W, 3)
+    dtypes = (torch.float32,) if coding == "f32" else (torch.uint16, torch.int16)
+    if out is not None:
+        if not (isinstance(out, torch.Tensor) and out.dtype in dtypes and tuple(out.shape) == shape):
+            raise RuntimeError("%s: out must be a %s tensor of shape %s" % (who, str(dtypes[0]).replace("torch.", ""), shape))
+        if not out[0].is_contiguous():
+            raise RuntimeError("%s: every sample of out must be dense (strides %s)" % (who, out.stride()))
+    fbs = _plane4(flow, "flow")
+    if out is not None and not out.is_cuda:
+        raise RuntimeError("%s: expected a CUDA tensor for out" % who)
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty(shape, dtype=dtypes[0], device=flow.device)
+    obs = (out.stride(0) if N > 1 else 0) * out.element_size()
+    _check(lib.accflow_flow_export(_p(flow), fbs, Hp, Wp, y0, x0, H, W, _p(out), obs, int(coding == "u16"), scale,
+                                   int(bool(big_endian)), N, _stream()), "accflow_flow_export")
+    return out
+
+
 def downflow8(flow):
     lib = _lib.load()
     _plane4(flow, "flow")

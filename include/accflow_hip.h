@@ -484,6 +484,30 @@ int accflow_flow_maxrad_f32(const float* flow, long long f_bs, float clip, int s
 int accflow_flow_to_rgb_u8(const float* flow, long long f_bs, const float* maxrad, float clip, unsigned char* out,
                            long long o_bs, int planar, int bgr, int B, int H, int W, void* stream);
 
+/* ---- The two ends of a video run: 8-bit frames in, flow files out (csrc/frame_io.hip); one launch each ----
+ * Frames.  src: uint8, sample n at src + n * s_bs, row y at + y * s_row, all strides in BYTES and >= 0;
+ *   planar == 0: (N,H,W,3) packed, pixel x of a row at + 3 x;   planar != 0: (N,3,H,W), plane c at + c * s_plane.
+ * Any base address and any pitch (decoders hand out pitched and sliced buffers).  out: float32 (N,3,H+pad_t+pad_b,W+pad_l+pad_r),
+ * dense samples, batch stride o_bs in elements:
+ *     out[n,c,y,x] = g(src[n, clamp(y - pad_t, 0, H-1), clamp(x - pad_l, 0, W-1), bgr ? 2 - c : c])
+ * - replicate padding, the pads any non-negative integers.  normalize != 0: g(v) = 2 (v / 255) - 1, the division correctly
+ * rounded and every step rounded to fp32 (the bits of torch's 2 * (x / 255.0) - 1);  normalize == 0: g(v) = (float)v.
+ * A thread takes 4 output pixels of a row: where they are interior and their source bytes start on a dword it loads dwords,
+ * everywhere else bytes - the same bits either way - and stores 16 bytes per channel.  N <= 65535, padded H W < 2^31 / 3. */
+int accflow_frames_from_u8(const unsigned char* src, long long s_bs, long long s_row, long long s_plane, int planar, int bgr,
+                           int normalize, float* out, long long o_bs, int N, int H, int W, int pad_l, int pad_r, int pad_t,
+                           int pad_b, void* stream);
+
+/* Flow files.  flow: (N,2,Hp,Wp) fp32, dense channel blocks, batch stride f_bs in elements; (y0,x0,H,W): the crop window -
+ * `unpad` as arithmetic.  out: dense samples, sample n at out + n * o_bs BYTES.
+ *   coding 0: float32 (N,H,W,2) = (u, v) interleaved, the payload of a Middlebury .flo file (out, o_bs multiples of 4);
+ *   coding 1: uint16 (N,H,W,3) = (code(u), code(v), valid), code(f) = trunc(min(max(scale f + 32768, 0), 65535)) with the
+ *             product and the sum each rounded to fp32, valid = 1; a NaN or infinite component has code 0 and makes valid 0.
+ *             scale 64: KITTI's coding (the reference's writeFlowKITTI), 128: CVO's.  big_endian != 0 stores every sample
+ *             byte-swapped: the buffer is then a 16-bit PNG's scanline payload as it stands.  (out, o_bs multiples of 2.) */
+int accflow_flow_export(const float* flow, long long f_bs, int Hp, int Wp, int y0, int x0, int H, int W, void* out,
+                        long long o_bs, int coding, float scale, int big_endian, int N, void* stream);
+
 /* InstanceNorm2d (no affine, eps, biased var; extractor.py:36-39) over each (b,c) plane of `x`,
  * fused with what follows it in ResidualBlock.forward (extractor.py:56-63):
  *   mode 0: out = norm(x)                    (downsample branch)
