@@ -13,24 +13,27 @@ Scheduling (exact): `forward` evaluates all estimator pairs of t
 call - they are independent because the reference never passes flow_init (AccFlow_.py:184,188) - with each
 frame encoded once, and runs the context encoder once per frame; only the fusion chain is sequential.
 """
+import contextlib
+import functools
+import itertools
 import math
+import os
+import threading
+import types
 
 import torch
 import torch.nn as nn
 
 from .. import ops
+from ..parallel import run_pair_sharded, run_pair_sharded_stream, world
 from ._packs import PackCache, require_cuda, span
 from .modules import ZeroConv2d
 from .raft.extractor import BasicEncoder
 
-import contextlib
-import threading
-import os
-
 USE_S16_CHAIN = os.environ.get("ACCFLOW_S16_CHAIN", "1") == "1"   # (0: the round-3 fusion chain on fp32 activations, A/B)
 CONTEXT_SIDE_STREAM = os.environ.get("ACCFLOW_CONTEXT_STREAM", "1") == "1"   # (0: context encoder in the serial section, A/B)
 # FlowEncoder of flow_ini / dflow, the occlusion / error maps and the blending mask of ALL fusion steps evaluated in one batch ahead
-# of the sequential loop (AccFlow._fuse_chain_hoisted; they do not depend on the accumulated flow).  Measured
+# of the sequential loop (_StepInputs over all steps; they do not depend on the accumulated flow).  Measured
 # (profiles/r04_ab_chain_hoist.txt): -0.3 ms for one sequence at a time, nothing (+0.1 ms) when the chain runs underneath the
 # next sequence's estimator, whose kernels fill the batch-1 steps' idle slots anyway.  "auto": on, except inside
 # parallel.SequencePipeline; "1" / "0": always / never (A/B).
@@ -66,10 +69,61 @@ def pipeline_chain_arithmetic():
         _CHAIN_TLS.no_ksplit = prev
 
 
+def launch_chain_aside(model, images, by_pair, ready, flag, other_flags=None):
+    """model.fuse_chain(images, by_pair) as a chain_in_pipeline on the device's side stream, behind the event `ready` of the
+    estimator that made by_pair (parallel.SequencePipeline, AccFlow.forward_pair_sharded_stream).  flag: the device int32
+    the chain's f16x3 kernels report range violations to, None in the other modes; other_flags: the other ranks' flags of
+    the same sequence.  Their sum goes to pinned memory behind the chain: no host synchronisation.  -> (done event, pinned
+    sum or None, outputs); the caller appends a tuple that starts with `images` and keeps alive what it allocated on its
+    own stream and the chain reads: harvest_chain_aside's handle."""
+    dev = images[0].device
+    main = torch.cuda.current_stream(dev)
+    side = _context_stream(dev)
+    side.wait_event(ready)
+    host = None
+    with torch.cuda.stream(side), chain_in_pipeline(), (ops.guard_scope(flag) if flag is not None else contextlib.nullcontext()):
+        outs = model.fuse_chain(images, by_pair)
+        if flag is not None:
+            tripped = flag
+            if other_flags:
+                tripped = flag + (torch.cat([f.reshape(-1) for f in other_flags]) != 0).sum().to(torch.int32)
+            host = torch.empty(1, dtype=torch.int32, pin_memory=True)
+            host.copy_(tripped, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record(side)
+    # the outputs live in blocks of the SIDE stream's allocator pool but are consumed by the caller on `main`
+    # (whatever stream that is): tell the allocator, so that freeing them while the caller's kernels still read
+    # them cannot hand the block to the next chain (the harvest only synchronises the HOST with the chain)
+    for o in outs:
+        o.record_stream(main)
+    return done, host, outs
+
+
+def harvest_chain_aside(model, handle, trip_name=None):
+    """The outputs of a handle (see launch_chain_aside), once its chain has finished.  A value left the fp16 split's range:
+    this sequence again in bf16x6, listed in ops.guard_report() as trip_name if one is given."""
+    done, host, outs, keep = handle
+    done.synchronize()
+    if host is not None and int(host.item()):
+        if trip_name is not None:
+            ops.note_guard_trip(trip_name)
+        with ops.conv_mode(ops.CONV_BF16X6), pipeline_chain_arithmetic():    # (every output of the pipelined modes: one arithmetic)
+            outs = model(images=keep[0])
+    return outs
+
+
+def flows_by_pair(small, pairs):
+    """estimate_small's pair-major (len(pairs) * N, 2, h, w) flows as {pair: (N, 2, h, w)}"""
+    N = small.shape[0] // len(pairs)
+    return {p: small[k * N:(k + 1) * N] for k, p in enumerate(pairs)}
+
+
 def _hoist_now():
     if USE_CHAIN_HOIST == "auto":
         return not getattr(_CHAIN_TLS, "pipelined", False)
-    return USE_CHAIN_HOIST == "1" or USE_CHAIN_HOIST is True
+    return USE_CHAIN_HOIST == "1"
+
+
 USE_CHAIN_DEFER_UP = os.environ.get("ACCFLOW_CHAIN_DEFER_UP", "1") == "1"   # (0: every fusion step upsamples its own flow, A/B)
 _CTX_STREAMS = {}
 
@@ -109,7 +163,6 @@ class FlowDecoder(nn.Module):
         t = ops.conv2d(pk.conv("m0", self.mask[0]), x, act=ops.ACT_RELU, out=t)
         mask = ops.conv2d(pk.conv("m2", self.mask[2]), t)  # no 0.25 factor here (AccFlow_.py:42-43)
         return flow_small, ops.convex_upsample(flow_small, mask)
-
 
     def _forward16(self, x16):
         """Pre-split form: the first convolutions of the flow and the mask head read the same tensor - ONE 128 -> 512
@@ -321,14 +374,10 @@ class Blending(nn.Module):
         require_cuda(f1, f2, emap)
         pk = self._packs
         if ops.s16_active() and USE_S16_CHAIN:
-            e16 = ops.to_s16(emap.float())
-            B, _, h, w = e16.shape
-            t16 = ops.S16.empty(B, self.mask[0].out_channels, h, w, e16.device)
-            ops.conv2d_multi(pk.multi("0m", self.mask[0]), [e16], act=ops.ACT_RELU, out16=t16, fp32_out=False)
-            t = t16
+            m = self.mask16(emap)
         else:
             t = ops.conv2d(pk.conv("0", self.mask[0]), emap.float(), act=ops.ACT_RELU)
-        m = ops.conv2d(pk.conv("2", self.mask[2]), t, act=ops.ACT_SIGMOID)
+            m = ops.conv2d(pk.conv("2", self.mask[2]), t, act=ops.ACT_SIGMOID)
         return ops.blend(f1.float().contiguous(), f2.float().contiguous(), m)
 
 
@@ -347,6 +396,49 @@ def downflow8(flow, mode="bilinear"):
     h, w = flow.shape[-2:]
     assert h % 8 == 0 and w % 8 == 0
     return ops.downflow8(flow.float().contiguous())
+
+
+class _StepInputs:
+    """What the pre-split fusion step (AccFlow._fuse16) reads that does not depend on the accumulated flow F2n
+    (AccFlow_.py:191-200): f_ini, the FlowEncoder features of flow_ini (fp32); df16, those of dflow; o16, the occlusion map;
+    mask, the blending mask.  The maps are read by convolutions only: their producers write them PRE-SPLIT (round 6).
+    Each member is computed where it is first read.  The stepwise chain makes one holder per step: FlowEncoder takes
+    [flow_ini, dflow, F2n] as one batch of 3N and every map is made right in front of its reader.  The hoisted chain makes
+    ONE over the K = (n - 2) N items of all steps and reads every member ahead of the sequential loop - FlowEncoder, one batch
+    of 2K, getOcc x 2, Blending.mask16 - and hands each step its items(); per step there remain FlowEncoder(F2n), AccPlus,
+    the blend and the decoder.  Same operators on the same values, no added work.  (Convolving the df / o / c members of
+    AccPlus's concatenations ahead of the loop as partial sums: built in round 4, no gain
+    (profiles/r04_ab_chain_prefold.txt), removed in round 6.)"""
+
+    def __init__(self, acc, flow_ini, dflow, c1, c2, cn):
+        self.acc, self.c1, self.c2, self.cn = acc, c1, c2, cn
+        self.flow_ini, self.dflow = flow_ini.float().contiguous(), dflow.float().contiguous()
+
+    def encode(self, F2n=None):
+        """FlowEncoder over flow_ini, dflow and - in the same batch - F2n -> F2n's features (fp32, pre-split)"""
+        K = self.dflow.shape[0]
+        flows = torch.cat([self.flow_ini, self.dflow] + ([] if F2n is None else [F2n]), dim=0)
+        feats, feats16 = self.acc.flow_encoder.encode16(flows)
+        self.f_ini, self.df16 = feats[:K], feats16.batch(K, 2 * K)
+        return None if F2n is None else (feats[2 * K:], feats16.batch(2 * K, 3 * K))
+
+    def _map16(self, flow, i2, binary):
+        K, _, h, w = flow.shape
+        out16 = ops.S16.empty(K, 1 if binary else self.c1.shape[1], h, w, flow.device)
+        return ops.get_occ(flow, self.c1, i2, binary=binary, out16=out16)
+
+    @functools.cached_property
+    def o16(self):
+        return self._map16(self.dflow, self.c2, True)
+
+    @functools.cached_property
+    def mask(self):
+        return self.acc.blending.mask16(self._map16(self.flow_ini, self.cn, False))
+
+    def items(self, k0, k1):
+        """Items k0 .. k1 of a holder computed ahead: a step with these encodes F2n alone."""
+        return types.SimpleNamespace(encode=self.acc.flow_encoder.encode16, f_ini=self.f_ini[k0:k1], df16=self.df16.batch(k0, k1),
+                                     o16=self.o16.batch(k0, k1), mask=self.mask[k0:k1])
 
 
 class AccFlow(nn.Module):
@@ -371,31 +463,25 @@ class AccFlow(nn.Module):
         self.mixed_precision = True
 
     # ---- one fusion step given all its inputs (AccFlow_.py:191-201) -----------------------------
-    def _fuse(self, dflow, flow_ini, F2n, c1, c2, cn, c1_16=None, defer=None):
-        """defer = (x16 slice, flow slice): write the fused features (pre-split) and the 1/8-resolution flow there and return
-        (flow_small, None) - the caller upsamples all steps in one batch (fuse_chain)."""
-        if c1_16 is not None and ops.s16_active() and USE_S16_CHAIN:
-            N = dflow.shape[0]
-            feats, feats16 = self.flow_encoder.encode16(torch.cat([flow_ini, dflow, F2n], dim=0).float().contiguous())
-            f_ini, f = feats[:N], feats[2 * N:]
-            h, w = dflow.shape[2:]
-            # the occlusion and error maps, the blending mask and the fused features are read by convolutions only: they
-            # are written PRE-SPLIT by their producers (round 6: no fp32 tensor + to_s16 pass in between)
-            o16 = ops.get_occ(dflow.float(), c1, c2, binary=True, out16=ops.S16.empty(N, 1, h, w, dflow.device))
-            f_acc = self.accplus.forward16(feats16.batch(N, 2 * N), f, feats16.batch(2 * N, 3 * N), o16, c1_16)
-            e16 = ops.get_occ(flow_ini.float(), c1, cn, binary=False, out16=ops.S16.empty(N, c1.shape[1], h, w, dflow.device))
-            m = self.blending.mask16(e16)
-            x16 = defer[0] if defer is not None else ops.S16.empty(N, f_acc.shape[1], h, w, dflow.device)
-            ops.blend(f_ini.contiguous(), f_acc, m, out16=x16)
-            if defer is not None:
-                return self.flow_decoder.flow16(x16, out=defer[1]), None
-            return self.flow_decoder._forward16(x16)
+    def _fuse(self, dflow, flow_ini, F2n, c1, c2, cn):
+        """The module-form step, the reference's iter body: iter(), the warm-start schedule and the chain on fp32 activations."""
         f_ini, df, f = self.flow_encoder([flow_ini, dflow, F2n])
         o = getOcc(dflow, c1, c2)
         f_acc = self.accplus(df, f, o, c1)
         emap = getOcc(flow_ini, c1, cn, binary=False)
         f_fuse = self.blending(f_ini, f_acc, emap)
         return self.flow_decoder(f_fuse)
+
+    def _fuse16(self, inputs, F2n, c1_16, x16, small=None):
+        """The pre-split step: every chain of the f16x3 mode.  inputs: _StepInputs, where the order of the launches in front
+        of AccPlus and of the blend is decided; x16: where the fused features go.  small: the decoder's flow head alone
+        writes the 1/8-resolution flow there, returns (small, None) - the caller upsamples all steps in one batch."""
+        f, f16 = inputs.encode(F2n)
+        f_acc = self.accplus.forward16(inputs.df16, f, f16, inputs.o16, c1_16)
+        ops.blend(inputs.f_ini, f_acc, inputs.mask, out16=x16)
+        if small is not None:
+            return self.flow_decoder.flow16(x16, out=small), None
+        return self.flow_decoder._forward16(x16)
 
     @torch.no_grad()
     @ops.range_guarded
@@ -434,6 +520,10 @@ class AccFlow(nn.Module):
                              iters=iters, flow_init=flow_init)
         return downflow8(flows)
 
+    def context_of(self, images, want16=True):
+        """The context encoder's features per frame; want16: (fp32 features, pre-split features or None), what fuse_chain takes."""
+        return self.context([im.float().contiguous() for im in images], want16=want16)
+
     # ---- the context encoder does not depend on any flow (AccFlow_.py:191: c1, c2, cn = self.context([I1, I2, In])): it runs
     # on a side stream UNDERNEATH the estimator of the same sequence instead of in the serial section behind it
     def context_async(self, images):
@@ -448,7 +538,7 @@ class AccFlow(nn.Module):
         with torch.cuda.stream(side):
             flag = torch.zeros(1, dtype=torch.int32, device=dev) if guarded else None
             with (ops.guard_scope(flag) if guarded else contextlib.nullcontext()):
-                ctx = self.context([im.float().contiguous() for im in images], want16=True)
+                ctx = self.context_of(images)
         return (side, ctx, flag, images)
 
     def context_join(self, handle):
@@ -458,15 +548,21 @@ class AccFlow(nn.Module):
         if flag is not None and int(flag.item()):        # the context stage alone falls back to bf16x6 (on this stream)
             ops.note_guard_trip("AccFlow.context")
             with ops.conv_mode(ops.CONV_BF16X6):
-                return self.context([im.float().contiguous() for im in images], want16=True)
+                return self.context_of(images)
         # the outputs live in blocks of the side stream's allocator pool and are read on `main`: tell the allocator, so that
         # freeing them cannot hand a block to another side-stream allocation while main's kernels still read it
-        for t in ctx[0]:
+        for t in list(ctx[0]) + [t.data for t in ctx[1] or ()]:
             t.record_stream(main)
-        if ctx[1] is not None:
-            for t in ctx[1]:
-                t.data.record_stream(main)
         return ctx
+
+    def estimate_with_context(self, images, pairs, ctx_images=None, **estimator):
+        """estimate_small(images, pairs, **estimator) with the context encoder of ctx_images (default: all of them) underneath
+        it on the side stream - behind it on this stream with CONTEXT_SIDE_STREAM off.  -> ({pair: flow}, context features)"""
+        ctx_images = images if ctx_images is None else ctx_images
+        handle = self.context_async(ctx_images) if CONTEXT_SIDE_STREAM else None
+        small = self.estimate_small(images, pairs, **estimator)
+        ctx = self.context_join(handle) if handle is not None else self.context_of(ctx_images)
+        return flows_by_pair(small, pairs), ctx
 
     @torch.no_grad()
     @ops.range_guarded
@@ -476,77 +572,61 @@ class AccFlow(nn.Module):
         decoder's 1/8-resolution flow of the LAST step) - what the next step of a longer chain starts from (AccFlowStream);
         the launches are the same either way."""
         if ctx is None:
-            ctx = self.context([im.float().contiguous() for im in images], want16=True)
-        if getattr(_CHAIN_TLS, "no_ksplit", False):      # (chain_in_pipeline / pipeline_chain_arithmetic: the chain proper only)
-            with ops.ksplit_scope(False):
-                return self._fuse_chain(images, by_pair, ctx, return_small)
-        return self._fuse_chain(images, by_pair, ctx, return_small)
+            ctx = self.context_of(images)
+        # (chain_in_pipeline / pipeline_chain_arithmetic: the chain proper only)
+        with (ops.ksplit_scope(False) if getattr(_CHAIN_TLS, "no_ksplit", False) else contextlib.nullcontext()):
+            return self._fuse_chain(images, by_pair, ctx, return_small)
 
     def _fuse_chain(self, images, by_pair, ctx, return_small=False):
+        """One loop over the steps i = 2 .. n-1, each from the 1/8-resolution flow F2n of the one before.  In the f16x3 mode
+        the steps are pre-split (_fuse16); with more than one step, what does not depend on F2n is hoisted out of the loop
+        (_hoist_now: one _StepInputs over all steps) and what no later step reads is deferred behind it (USE_CHAIN_DEFER_UP)."""
         n = len(images)
         ctx, ctx16 = ctx
         outs, F2n = [], by_pair[(1, 0)]
-        if ctx16 is not None and ops.s16_active() and USE_S16_CHAIN and _hoist_now() and n > 3:
-            return self._fuse_chain_hoisted(n, by_pair, ctx, ctx16, return_small)
-        defer = ctx16 is not None and ops.s16_active() and USE_S16_CHAIN and USE_CHAIN_DEFER_UP and n > 3
+        (N, _, h, w), dev = F2n.shape, F2n.device
+        s16 = ctx16 is not None and ops.s16_active() and USE_S16_CHAIN
+        hoist = s16 and n > 3 and _hoist_now()
+        defer = s16 and n > 3 and USE_CHAIN_DEFER_UP
+        steps = range(2, n)
+        if hoist:
+            # (views, not copies: the per-frame context features are consecutive slices of ONE encoder output)
+            cn = ctx[0].expand(len(steps), -1, -1, -1) if N == 1 else ctx[0].repeat(len(steps), 1, 1, 1)
+            ahead = _StepInputs(self, torch.cat([by_pair[(i, 0)] for i in steps], dim=0),
+                                torch.cat([by_pair[(i, i - 1)] for i in steps], dim=0),
+                                span([ctx[i] for i in steps]), span([ctx[i - 1] for i in steps]), cn)
+            ahead.encode(), ahead.o16, ahead.mask         # (every member read here, in front of the loop)
         if defer:
             # Only the 1/8-resolution flow of step i enters step i+1 (AccFlow_.py:171-175): the mask head and the convex
             # upsampling of every step leave the sequential loop and run once, batched over the steps, behind it
-            N, _, h, w = F2n.shape
-            x16_all = ops.S16.empty((n - 2) * N, self.hidden_channel, h, w, F2n.device)
-            small_all = torch.empty(((n - 2) * N, 2, h, w), dtype=torch.float32, device=F2n.device)
-        for i in range(2, n):
-            k0, k1 = (i - 2) * F2n.shape[0], (i - 1) * F2n.shape[0]
-            F2n, up = self._fuse(by_pair[(i, i - 1)].contiguous(), by_pair[(i, 0)].contiguous(), F2n.contiguous(),
-                                 ctx[i], ctx[i - 1], ctx[0], c1_16=ctx16[i] if ctx16 is not None else None,
-                                 defer=(x16_all.batch(k0, k1), small_all[k0:k1]) if defer else None)
+            x16_all = ops.S16.empty(len(steps) * N, self.hidden_channel, h, w, dev)
+            small_all = torch.empty((len(steps) * N, 2, h, w), dtype=torch.float32, device=dev)
+        for k, i in enumerate(steps):
+            k0, k1 = k * N, (k + 1) * N
+            if s16:
+                inputs = ahead.items(k0, k1) if hoist else _StepInputs(self, by_pair[(i, 0)], by_pair[(i, i - 1)], ctx[i],
+                                                                       ctx[i - 1], ctx[0])
+                x16 = x16_all.batch(k0, k1) if defer else ops.S16.empty(N, self.hidden_channel, h, w, dev)
+                F2n, up = self._fuse16(inputs, F2n.float().contiguous(), ctx16[i], x16, small_all[k0:k1] if defer else None)
+            else:
+                F2n, up = self._fuse(by_pair[(i, i - 1)].contiguous(), by_pair[(i, 0)].contiguous(), F2n.contiguous(),
+                                     ctx[i], ctx[i - 1], ctx[0])
             outs.append(up)
         if defer:
             outs = list(self.flow_decoder.upsample16(x16_all, small_all).split(N, dim=0))
         return (outs, F2n) if return_small else outs
 
-    def _fuse_chain_hoisted(self, n, by_pair, ctx, ctx16, return_small=False):
-        """fuse_chain with what does not depend on the accumulated flow F2n taken out of the sequential loop and batched over
-        the n - 2 steps (AccFlow_.py:191-200 per step: flow_ini, dflow, the context features - hence the occlusion map, the
-        error map and the blending mask - are known once the estimator has run): FlowEncoder over [flow_ini, dflow] of all
-        steps (one batch of 2 (n-2) N instead of n-2 batches of 2N next to F2n's N), getOcc x 2, Blending.mask ahead of the
-        loop; the mask head + convex upsampling behind it (USE_CHAIN_DEFER_UP).  Per step there remain FlowEncoder(F2n),
-        AccPlus, the blend and the flow head.  Same operators on the same values, no added work.  (Convolving the df / o / c
-        members of AccPlus's concatenations ahead of the loop as partial sums was built in round 4, measured - no gain,
-        profiles/r04_ab_chain_prefold.txt - and removed in round 6.)"""
-        steps = list(range(2, n))
-        N = by_pair[(1, 0)].shape[0]
-        K = len(steps) * N
-        flow_ini = torch.cat([by_pair[(i, 0)] for i in steps], dim=0).float().contiguous()
-        dflow = torch.cat([by_pair[(i, i - 1)] for i in steps], dim=0).float().contiguous()
-        feats, feats16 = self.flow_encoder.encode16(torch.cat([flow_ini, dflow], dim=0))
-        f_ini, df16 = feats[:K], feats16.batch(K, 2 * K)
-        # (views, not copies: the per-frame context features are consecutive slices of ONE encoder output)
-        c1 = span([ctx[i] for i in steps])
-        c2 = span([ctx[i - 1] for i in steps])
-        cn = ctx[0].expand(len(steps), -1, -1, -1) if N == 1 else ctx[0].repeat(len(steps), 1, 1, 1)
-        h, w = dflow.shape[2:]
-        o16 = ops.get_occ(dflow, c1, c2, binary=True, out16=ops.S16.empty(K, 1, h, w, dflow.device))
-        m = self.blending.mask16(ops.get_occ(flow_ini, c1, cn, binary=False, out16=ops.S16.empty(K, c1.shape[1], h, w, dflow.device)))
-        outs, F2n = [], by_pair[(1, 0)]
-        defer = USE_CHAIN_DEFER_UP
-        if defer:
-            _, _, h, w = F2n.shape
-            x16_all = ops.S16.empty(K, self.hidden_channel, h, w, F2n.device)
-            small_all = torch.empty((K, 2, h, w), dtype=torch.float32, device=F2n.device)
-        for k, i in enumerate(steps):
-            k0, k1 = k * N, (k + 1) * N
-            f, f16 = self.flow_encoder.encode16(F2n.float().contiguous())
-            f_acc = self.accplus.forward16(df16.batch(k0, k1), f, f16, o16.batch(k0, k1), ctx16[i])
-            if defer:
-                F2n = self.flow_decoder.flow16(ops.blend(f_ini[k0:k1], f_acc, m[k0:k1], out16=x16_all.batch(k0, k1)),
-                                               out=small_all[k0:k1])
-            else:
-                F2n, up = self.flow_decoder(ops.blend(f_ini[k0:k1], f_acc, m[k0:k1]))
-                outs.append(up)
-        if defer:
-            outs = list(self.flow_decoder.upsample16(x16_all, small_all).split(N, dim=0))
-        return (outs, F2n) if return_small else outs
+    def _warm_chain(self, images, adj, ctx, F2n, feats, seed_iters):
+        """The warm-start loop (see the class docstring): per frame i the seed by compose_flow, the seeded estimate i -> 0 of
+        seed_iters iterations and the module-form step, starting from F2n = F(1 -> 0).  -> (outputs, the last step's F2n)"""
+        outs = []
+        for i in range(2, len(images)):
+            dflow = adj[(i, i - 1)].contiguous()
+            seed = ops.compose_flow(dflow, F2n.contiguous())
+            flow_ini = self.estimate_small(images, [(i, 0)], flow_init=seed, iters=seed_iters, features=feats)
+            F2n, up = self._fuse(dflow, flow_ini.contiguous(), F2n.contiguous(), ctx[i], ctx[i - 1], ctx[0])
+            outs.append(up)
+        return outs, F2n
 
     @torch.no_grad()
     @ops.range_guarded
@@ -558,20 +638,11 @@ class AccFlow(nn.Module):
         n = len(images)
         if n < 3:
             return []
-        N = images[0].shape[0]
         feats = {}
         adjacent = [(i, i - 1) for i in range(1, n)]
-        small = self.estimate_small(images, adjacent, features=feats)
-        adj = {p: small[k * N:(k + 1) * N] for k, p in enumerate(adjacent)}
-        ctx = self.context([im.float().contiguous() for im in images])
-        outs, F2n = [], adj[(1, 0)]
-        for i in range(2, n):
-            dflow = adj[(i, i - 1)].contiguous()
-            seed = ops.compose_flow(dflow, F2n.contiguous())
-            flow_ini = self.estimate_small(images, [(i, 0)], flow_init=seed, iters=self.warm_iters, features=feats)
-            F2n, up = self._fuse(dflow, flow_ini.contiguous(), F2n.contiguous(), ctx[i], ctx[i - 1], ctx[0])
-            outs.append(up)
-        return outs
+        adj = flows_by_pair(self.estimate_small(images, adjacent, features=feats), adjacent)
+        ctx = self.context_of(images, want16=False)
+        return self._warm_chain(images, adj, ctx, adj[(1, 0)], feats, self.warm_iters)[0]
 
     @staticmethod
     def stack_frames(images):
@@ -594,14 +665,10 @@ class AccFlow(nn.Module):
         if self.warm_start:
             return self.forward_warm(images)
         images = self.stack_frames(images)
-        N = images[0].shape[0]
-        pairs = self.pair_schedule(len(images))
 
         def run():
-            handle = self.context_async(images) if CONTEXT_SIDE_STREAM else None
-            small = self.estimate_small(images, pairs)
-            ctx = self.context_join(handle) if handle is not None else None
-            return self.fuse_chain(images, {p: small[k * N:(k + 1) * N] for k, p in enumerate(pairs)}, ctx=ctx)
+            flows, ctx = self.estimate_with_context(images, self.pair_schedule(len(images)))
+            return self.fuse_chain(images, flows, ctx=ctx)
 
         # first without a host synchronisation per stage; only if some value left the fp16 split's range, stage by stage
         out, tripped = ops.optimistic(run, images[0].device)
@@ -638,16 +705,10 @@ class AccFlow(nn.Module):
         Returns {k: outputs of sequence k} for the sequences this rank was the root of.  `sequences` may be any iterable (a
         data loader: it is consumed one sequence at a time); pending chains are resolved with a bounded lag, and with
         on_result(k, outputs) nothing is retained here - memory does not grow with the stream's length."""
-        import itertools
-        from .. import ops
-        from ..parallel import run_pair_sharded_stream
         it = iter(sequences)
         first = list(next(it))
         sequences = itertools.chain([first], (list(s) for s in it))
         dev, n_frames = first[0].device, len(first)
-        if getattr(self, "_stream_side", None) is None:
-            self._stream_side = _context_stream(dev)      # (ONE side stream per device in the process: hardware queues, see there)
-        side = self._stream_side
         guarded = ops.current_mode() == ops.CONV_F16X3
 
         # f16x3 range guard without a host synchronisation: every rank's estimator pairs report to a device flag that rides
@@ -665,54 +726,31 @@ class AccFlow(nn.Module):
             return small, flag
 
         def fuse(images, bp, flags):
-            main = torch.cuda.current_stream(dev)
             flag = torch.zeros(1, dtype=torch.int32, device=dev)
             ready = torch.cuda.Event()
-            ready.record(main)
-            side.wait_event(ready)
-            host = None
-            with torch.cuda.stream(side), chain_in_pipeline(), (ops.guard_scope(flag) if guarded else contextlib.nullcontext()):
-                outs = self.fuse_chain(images, bp)
-                if guarded:
-                    tripped = flag + (torch.cat([f.reshape(-1) for f in flags]) != 0).sum().to(torch.int32)
-                    host = torch.empty(1, dtype=torch.int32, pin_memory=True)
-                    host.copy_(tripped, non_blocking=True)
-                done = torch.cuda.Event()
-                done.record(side)
-            for o in outs:
-                o.record_stream(main)
-            return (done, host, outs, (images, bp, flag, flags))
-
-        def harvest(h):
-            done, host, outs, keep = h
-            done.synchronize()
-            if host is not None and int(host.item()):      # a value left the fp16 split's range: this sequence again in bf16x6
-                ops.note_guard_trip("AccFlow.forward_pair_sharded_stream")
-                with ops.conv_mode(ops.CONV_BF16X6), pipeline_chain_arithmetic():    # (every output of the mode: one arithmetic)
-                    outs = self(images=keep[0])
-            return outs
+            ready.record(torch.cuda.current_stream(dev))
+            # (the chain on the ONE side stream per device of the process: hardware queues, see _context_stream)
+            return launch_chain_aside(self, images, bp, ready, flag if guarded else None, flags) + ((images, bp, flag, flags),)
 
         shares = hasattr(getattr(self, "ofe", None), "att")
         return run_pair_sharded_stream(est, fuse, self.pair_schedule(n_frames), sequences, group=group,
-                                       keep_together=shares, harvest=harvest, on_result=on_result)
+                                       keep_together=shares, on_result=on_result,
+                                       harvest=lambda h: harvest_chain_aside(self, h, "AccFlow.forward_pair_sharded_stream"))
 
     @torch.no_grad()
     def forward_pair_sharded(self, images, dst=0, group=None):
         """One sequence batch spread over the ranks of `group`: estimator pairs are dealt round-robin, one
         all_gather of the 1/8-res flows, fusion chain on `dst` (returns None on the other ranks)."""
-        from ..parallel import run_pair_sharded
         images = list(images)
         N = images[0].shape[0]
         h, w = images[0].shape[2] // 8, images[0].shape[3] // 8
-
-        from ..parallel import world
         is_root = world(group)[1] == dst
         holder = []
 
         def est(my_pairs):
             # the root encodes the context features of all frames on its side stream WHILE it estimates its own pairs:
             # the serial section behind the all_gather is then the five fusion steps only
-            if is_root and CONTEXT_SIDE_STREAM and images[0].is_cuda and hasattr(self, "context_async") and not holder:
+            if is_root and CONTEXT_SIDE_STREAM and images[0].is_cuda and not holder:
                 holder.append(self.context_async(images))
             if not my_pairs:
                 return torch.zeros((0, N, 2, h, w), dtype=torch.float32, device=images[0].device)
@@ -821,19 +859,13 @@ class AccFlowStream:
             feats = st.features() if st is not None else {}
             if N > 1:
                 ctx, ctx16 = self._encode_per_sample(L, pairs, range(len(L) - len(todo), len(L)), feats, want16=True)
-                small = m.estimate_small(L, pairs, iters=self.iters, features=feats)
+                by_pair = flows_by_pair(m.estimate_small(L, pairs, iters=self.iters, features=feats), pairs)
             else:
-                handle = m.context_async(todo) if CONTEXT_SIDE_STREAM else None
-                small = m.estimate_small(L, pairs, iters=self.iters, features=feats)
-                if handle is not None:
-                    ctx, ctx16 = m.context_join(handle)
-                else:
-                    ctx, ctx16 = m.context([im.float().contiguous() for im in todo], want16=True)
+                by_pair, (ctx, ctx16) = m.estimate_with_context(L, pairs, ctx_images=todo, iters=self.iters, features=feats)
             ctx, ctx16 = list(ctx), list(ctx16) if ctx16 is not None else None
             if cached:
                 ctx = st.ctx + ctx
                 ctx16 = st.ctx16 + ctx16 if ctx16 is not None and st.ctx16 is not None else None
-            by_pair = {p: small[k * N:(k + 1) * N] for k, p in enumerate(pairs)}
             if st is not None:
                 by_pair[(1, 0)] = st.F2n
             outs, F2n = m.fuse_chain(L, by_pair, ctx=(ctx, ctx16), return_small=True)
@@ -860,19 +892,12 @@ class AccFlowStream:
             if N > 1:
                 ctx = self._encode_per_sample(L, adjacent + [(i, 0) for i in range(2, len(L))],
                                               range(2 if cached else 0, len(L)), feats, want16=False)[0]
-            small = m.estimate_small(L, adjacent, iters=self.iters, features=feats)
-            adj = {p: small[k * N:(k + 1) * N] for k, p in enumerate(adjacent)}
+            adj = flows_by_pair(m.estimate_small(L, adjacent, iters=self.iters, features=feats), adjacent)
             if N == 1:
-                ctx = list(m.context([im.float().contiguous() for im in (L[2:] if cached else L)]))
+                ctx = list(m.context_of(L[2:] if cached else L, want16=False))
             if cached:
                 ctx = st.ctx + ctx
-            outs, F2n = [], adj[(1, 0)] if st is None else st.F2n
-            for i in range(2, len(L)):
-                dflow = adj[(i, i - 1)].contiguous()
-                seed = ops.compose_flow(dflow, F2n.contiguous())
-                flow_ini = m.estimate_small(L, [(i, 0)], flow_init=seed, iters=warm_iters, features=feats)
-                F2n, up = m._fuse(dflow, flow_ini.contiguous(), F2n.contiguous(), ctx[i], ctx[i - 1], ctx[0])
-                outs.append(up)
+            outs, F2n = m._warm_chain(L, adj, ctx, adj[(1, 0)] if st is None else st.F2n, feats, warm_iters)
             return outs, (feats["fmap"], ctx, None, F2n, mode)
 
         outs, made = ops.with_range_guard(run, dev, name="AccFlowStream.push")
@@ -893,7 +918,7 @@ class AccFlowStream:
             frames = [f[n:n + 1] for f in L]
             fn = {k: ({i: t[n:n + 1] for i, t in v.items()} if isinstance(v, dict) else v) for k, v in feats.items()}
             per.append(m.ofe.encode_frames(frames, fnet_ids, cnet_ids, fn))
-            c = m.context([frames[i].float().contiguous() for i in ctx_ids], want16=want16)
+            c = m.context_of([frames[i] for i in ctx_ids], want16=want16)
             c, c16 = c if want16 else (c, None)
             ctx.append(c)
             ctx16.append(c16)

@@ -250,30 +250,24 @@ class SequencePipeline:
 
     def __init__(self, model):
         self.model = model
-        self.side = None
         self.pending = None
         self.count = 0
 
     @torch.no_grad()
     def _launch(self, images):
         from . import ops
+        from .networks.AccFlow_ import flows_by_pair, launch_chain_aside
         m = self.model
         images = list(images)
         dev = images[0].device
         if len(images) < 3 or getattr(m, "warm_start", False):   # nothing to overlap / seeded schedule: plain forward
             return (None, None, m(images=images), None)
-        if self.side is None:
-            from .networks.AccFlow_ import _context_stream
-            self.side = _context_stream(dev)     # (the process's one side stream per device: 4 streams = 4 hardware queues)
         main = torch.cuda.current_stream(dev)
         if hasattr(m, "stack_frames"):
             images = m.stack_frames(images)      # (one copy instead of one torch.cat per encoder)
-        N = images[0].shape[0]
         pairs = m.pair_schedule(len(images))
-        guarded = ops.current_mode() == ops.CONV_F16X3
-        flag = torch.zeros(1, dtype=torch.int32, device=dev) if guarded else None
-        scope = ops.guard_scope(flag) if guarded else contextlib.nullcontext()
-        with scope:
+        flag = torch.zeros(1, dtype=torch.int32, device=dev) if ops.current_mode() == ops.CONV_F16X3 else None
+        with (ops.guard_scope(flag) if flag is not None else contextlib.nullcontext()):
             home, feats = main, None
             if PIPELINE_SPLIT and hasattr(m.ofe, "encode_pairs"):
                 # The estimator in two halves: the encoders on the caller's stream, the refinement "at home" on the first
@@ -296,37 +290,15 @@ class SequencePipeline:
                 small = m.estimate_small(images, pairs, features=feats)
                 ready = torch.cuda.Event()
                 ready.record(home)
-            by_pair = {p: small[k * N:(k + 1) * N] for k, p in enumerate(pairs)}
-            self.side.wait_event(ready)
-            host = None
-            from .networks.AccFlow_ import chain_in_pipeline
-            with torch.cuda.stream(self.side), chain_in_pipeline():
-                outs = m.fuse_chain(images, by_pair)
-                if guarded:
-                    host = torch.empty(1, dtype=torch.int32, pin_memory=True)
-                    host.copy_(flag, non_blocking=True)
-                done = torch.cuda.Event()
-                done.record(self.side)
-            # the outputs live in blocks of the SIDE stream's allocator pool but are consumed by the caller on `main`
-            # (whatever stream that is): tell the allocator, so that freeing them while the caller's kernels still read
-            # them cannot hand the block to the next chain (the harvest only synchronises the HOST with the chain)
-            for o in outs:
-                o.record_stream(main)
+        # the chain on the process's one side stream per device (4 streams = 4 hardware queues)
+        chain = launch_chain_aside(m, images, flows_by_pair(small, pairs), ready, flag)
         # `small`, `images`, `flag` were allocated on the main stream and are read by the side stream: they stay
         # referenced here until the chain has finished
-        return (done, host, outs, (images, small, flag, feats))
+        return chain + ((images, small, flag, feats),)
 
     def _harvest(self, p):
-        from . import ops
-        done, host, outs, keep = p
-        if done is None:
-            return outs
-        done.synchronize()
-        if host is not None and int(host.item()):
-            from .networks.AccFlow_ import pipeline_chain_arithmetic
-            with ops.conv_mode(ops.CONV_BF16X6), pipeline_chain_arithmetic():     # (every output of the pipeline: one arithmetic)
-                outs = self.model(images=keep[0])
-        return outs
+        from .networks.AccFlow_ import harvest_chain_aside
+        return p[2] if p[0] is None else harvest_chain_aside(self.model, p)
 
     def submit(self, images):
         prev, self.pending = self.pending, self._launch(images)

@@ -1469,9 +1469,10 @@ def test_corr_per_frame_packs(ops, mode):
 
 def test_folded_fusion_chain_matches_the_stepwise_chain(ops, monkeypatch):
     """AccFlow.fuse_chain hoists everything that does not depend on the accumulated flow out of the sequential loop
-    (AccFlow._fuse_chain_hoisted: FlowEncoder of flow_ini / dflow, the occlusion and error maps and the blending mask, batched
+    (one _StepInputs over all steps: FlowEncoder of flow_ini / dflow, the occlusion and error maps and the blending mask, batched
     over the steps).  Same operators on the same values, so both forms must agree far inside the parity budget; batch 2
-    exercises the (step, sample) indexing of the batched tensors."""
+    exercises the (step, sample) indexing of the batched tensors.  With and without the deferred upsampling: hoisted and not
+    deferred, every step blends into its own pre-split tensor and runs the whole decoder."""
     from accflow_amd.data.synthetic import make_sequence, normalize
     from accflow_amd.networks import AccFlow_ as A
     if not (ops.s16_active() and A.USE_S16_CHAIN):
@@ -1480,13 +1481,15 @@ def test_folded_fusion_chain_matches_the_stepwise_chain(ops, monkeypatch):
     frames = [dev(normalize(f)) for f in make_sequence(321, 5, 128, 192, batch=2)]
     monkeypatch.setattr(A, "USE_CHAIN_HOIST", "0")
     stepwise = [o.cpu() for o in model(frames)]
-    for hoist in ("1", "auto"):
+    for hoist, defer in (("1", True), ("auto", True), ("1", False), ("auto", False)):
         monkeypatch.setattr(A, "USE_CHAIN_HOIST", hoist)
+        monkeypatch.setattr(A, "USE_CHAIN_DEFER_UP", defer)
         got = [o.cpu() for o in model(frames)]
         assert len(got) == len(stepwise) == 3
         for a, b in zip(got, stepwise):
             me, mx = O.epe(a, b)
-            assert me <= 2e-5 and mx <= 2e-3, (hoist, me, mx)
+            print("hoist %s, deferral %s: EPE mean %.3e max %.3e" % (hoist, defer, me, mx))
+            assert me <= 2e-5 and mx <= 2e-3, (hoist, defer, me, mx)
 
 
 def test_deferred_upsampling_matches_the_per_step_decoder(ops, monkeypatch):
@@ -1499,7 +1502,7 @@ def test_deferred_upsampling_matches_the_per_step_decoder(ops, monkeypatch):
         pytest.skip("the deferred form belongs to the S16 chain")
     model, _ = _accflow("acc|raft")
     frames = [dev(normalize(f)) for f in make_sequence(654, 5, 128, 192, batch=2)]
-    monkeypatch.setattr(A, "USE_CHAIN_HOIST", "0")     # (the hoisted chain has its own copy of the deferral: both are run)
+    monkeypatch.setattr(A, "USE_CHAIN_HOIST", "0")     # (the deferral is the one loop's: with hoisting, see the test above)
     monkeypatch.setattr(A, "USE_CHAIN_DEFER_UP", True)
     deferred = [o.cpu() for o in model(frames)]
     monkeypatch.setattr(A, "USE_CHAIN_DEFER_UP", False)

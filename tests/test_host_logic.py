@@ -310,7 +310,7 @@ def test_schedule_scopes_are_thread_local_and_restore():
         pass
     assert ops._ksplit_on() == ops.USE_KSPLIT
     flag = lambda: getattr(A._CHAIN_TLS, "no_ksplit", False)
-    assert not flag() and A._hoist_now() == (A.USE_CHAIN_HOIST in ("auto", "1", True))
+    assert not flag() and A._hoist_now() == (A.USE_CHAIN_HOIST in ("auto", "1"))
     with A.chain_in_pipeline():
         assert flag() == (not A.PIPELINE_CHAIN_KSPLIT)
         if A.USE_CHAIN_HOIST == "auto":
