@@ -175,6 +175,7 @@ SIGNATURES = {
     "accflow_blend_backward_f32": [c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f],
     "accflow_convex_upsample_backward_f32": [c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_f],
     "accflow_conv_wgrad_f32": [c_f, c_ll, c_f, c_ll, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f],
+    "accflow_conv_wgrad_plan": [c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_ll, c_ll, ctypes.POINTER(c_i), c_i],
     "accflow_deform_conv_backward_f32": [c_f, c_ll, c_f, c_ll, c_f, c_ll, c_f, c_f, c_ll, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
                                          c_i, c_f],
 }

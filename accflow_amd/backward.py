@@ -101,6 +101,26 @@ def conv_wgrad(x, dy, KH, KW, stride=1, padding=(0, 0), bias=True):
     return dw, db
 
 
+WGRAD_KERNELS = ("general", "fast128", "fast64")   # ACCFLOW_WGRAD_GENERAL / _FAST128 / _FAST64 of include/accflow_hip.h
+
+
+def conv_wgrad_plan(B, Cin, Cout, H, W, KH, KW, stride=1, padding=(0, 0), x_bs=None, dy_bs=None):
+    """What conv_wgrad launches for this shape (accflow_conv_wgrad_plan: the launcher's own host function, no device call):
+    {"kernel": one of WGRAD_KERNELS, "terms", "grid": (x, y, z), "steps_per_part", "steps"}.  Part z of the pixel axis runs
+    the 16-pixel steps [z * steps_per_part, min((z + 1) * steps_per_part, steps)).  x_bs / dy_bs: batch strides in elements
+    (default: dense).  Raises RuntimeError for a shape the launch refuses."""
+    import ctypes
+    lib = _lib.load()
+    pH, pW = (padding, padding) if isinstance(padding, int) else padding
+    OH, OW = ((H + 2 * pH - KH) // stride + 1, (W + 2 * pW - KW) // stride + 1) if stride > 0 else (0, 0)
+    out = (ctypes.c_int * 7)()
+    _check(lib.accflow_conv_wgrad_plan(B, Cin, Cout, H, W, KH, KW, int(stride), int(pH), int(pW),
+                                       Cin * H * W if x_bs is None else int(x_bs),
+                                       Cout * OH * OW if dy_bs is None else int(dy_bs), out, 7), "accflow_conv_wgrad_plan")
+    return {"kernel": WGRAD_KERNELS[out[0]], "terms": out[1], "grid": (out[2], out[3], out[4]), "steps_per_part": out[5],
+            "steps": out[6]}
+
+
 GRAD_CONV_MODE = "bf16x6"   # the input-gradient convolutions: fp32-equivalent products with no range condition
 
 _DGRAD_CACHE = {}   # (tag, ids of the parameters a weight derives from) -> [their (data_ptr, version), value]: the five fusion

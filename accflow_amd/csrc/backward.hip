@@ -90,33 +90,36 @@ __global__ __launch_bounds__(256) void convex_upsample_backward_kernel(const flo
   float g[2];
 #pragma unroll
   for (int c = 0; c < 2; ++c) g[c] = dup[((long long)(n * 2 + c) * (8 * H8) + 8 * h + a) * W + 8 * w + b];
-  float m[9], mx = -INFINITY;
+  // softmax, t and d mask in double: near one-hot weights make d mask heavy-tailed (largest element 37 x its RMS with logits of
+  // +-100) and s_k (t_k - sum_j s_j t_j) a difference of nearly equal numbers - fp32 left it 1.3e-5 of the RMS from float64; the
+  // kernel moves 2 x 576 values per coarse pixel through memory, the 9 exponentials do not show
+  double m[9], mx = -INFINITY;
 #pragma unroll
   for (int k = 0; k < 9; ++k) {
-    m[k] = mask[((long long)n * 576 + k * 64 + ab) * P + pix];
-    mx = fmaxf(mx, m[k]);
+    m[k] = (double)mask[((long long)n * 576 + k * 64 + ab) * P + pix];
+    mx = fmax(mx, m[k]);
   }
-  float s = 0.0f;
+  double s = 0.0;
 #pragma unroll
-  for (int k = 0; k < 9; ++k) { m[k] = expf(m[k] - mx); s += m[k]; }
-  float t[9], dot = 0.0f;
+  for (int k = 0; k < 9; ++k) { m[k] = exp(m[k] - mx); s += m[k]; }
+  double t[9], dot = 0.0;
 #pragma unroll
   for (int k = 0; k < 9; ++k) {
     m[k] /= s;
     const int yy = h + k / 3 - 1, xx = w + k % 3 - 1;
     const bool ok = (unsigned)yy < (unsigned)H8 && (unsigned)xx < (unsigned)W8;
-    t[k] = 0.0f;
+    t[k] = 0.0;
     if (ok) {
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
-        t[k] += g[c] * 8.0f * flow[((long long)n * 2 + c) * P + yy * W8 + xx];
-        atomicAdd(&dflow[((long long)n * 2 + c) * P + yy * W8 + xx], 8.0f * m[k] * g[c]);
+        t[k] += (double)g[c] * 8.0 * (double)flow[((long long)n * 2 + c) * P + yy * W8 + xx];
+        atomicAdd(&dflow[((long long)n * 2 + c) * P + yy * W8 + xx], (float)(8.0 * m[k] * (double)g[c]));
       }
     }
     dot += m[k] * t[k];
   }
 #pragma unroll
-  for (int k = 0; k < 9; ++k) dmask[((long long)n * 576 + k * 64 + ab) * P + pix] = m[k] * (t[k] - dot);
+  for (int k = 0; k < 9; ++k) dmask[((long long)n * 576 + k * 64 + ab) * P + pix] = (float)(m[k] * (t[k] - dot));
 }
 
 // Weight gradient of a convolution: dw[co][ci][ky][kx] = sum_{b,y,x} dy[b,co,y,x] * x[b,ci,y*stride+ky-padH,x*stride+kx-padW]
@@ -443,6 +446,17 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_mfma_fast_kernel(const floa
 // float atomics), of the offsets (dy first, then dx: d sample / d h, d w with the floor cell held fixed - what autograd of the
 // bilinear formula gives) and of the modulation mask.  Thread = (b, tap, pixel), loop over the channels.
 constexpr int DEFORM_CG = 16;
+// One coordinate of a sample, position = tap position `base` (an integer) + offset, as the cell below it and the fraction inside
+// the cell: cell = base + floor(offset), frac = offset - floor(offset) - exact to 2^-24 px wherever the sample lies.  The sum
+// (float)base + offset instead is a multiple of 2^-16 px at coordinates of 128 .. 256 (of 2^-14 at 512 ..): its rounding moved
+// d offset of a 241-pixel-wide plane by 1.1e-4 of its RMS against float64 (d mask 6.7e-5, d x 4.6e-5).
+// Returns whether -1 < position < size (torchvision's condition for a sample to count); a NaN or huge offset is outside.
+__device__ __forceinline__ bool deform_cell(int base, float offset, int size, int& cell, float& frac) {
+  const float fo = floorf(offset);
+  cell = base + (int)fminf(fmaxf(fo, -1.0e9f), 1.0e9f);
+  frac = offset - fo;
+  return cell <= size - 1 && (cell >= 0 || (cell == -1 && frac > 0.0f));
+}
 __global__ __launch_bounds__(256) void deform_backward_kernel(const float* __restrict__ x, long long x_bs,
                                                               const float* __restrict__ off, long long off_bs,
                                                               const float* __restrict__ msk, long long msk_bs,
@@ -459,13 +473,13 @@ __global__ __launch_bounds__(256) void deform_backward_kernel(const float* __res
   const int y = p / W, xx = p - y * W, ky = tap / KW, kx = tap - ky * KW;
   const float dyo = off[b * off_bs + (long long)(2 * tap) * HW + p], dxo = off[b * off_bs + (long long)(2 * tap + 1) * HW + p];
   const float m = msk[b * msk_bs + (long long)tap * HW + p];
-  const float h = (float)(y - padH + ky) + dyo, w = (float)(xx - padW + kx) + dxo;
-  const bool inside = h > -1.0f && h < (float)H && w > -1.0f && w < (float)W;
+  int hl, wl;
+  float lh, lw;
+  const bool inside_h = deform_cell(y - padH + ky, dyo, H, hl, lh), inside_w = deform_cell(xx - padW + kx, dxo, W, wl, lw);
   float g_h = 0.0f, g_w = 0.0f, g_m = 0.0f;
-  if (inside) {
-    const float fh = floorf(h), fw = floorf(w);
-    const int hl = (int)fh, wl = (int)fw, hh = hl + 1, wh = wl + 1;
-    const float lh = h - fh, lw = w - fw, uh = 1.0f - lh, uw = 1.0f - lw;
+  if (inside_h && inside_w) {
+    const int hh = hl + 1, wh = wl + 1;
+    const float uh = 1.0f - lh, uw = 1.0f - lw;
     const bool o1 = hl >= 0 && wl >= 0, o2 = hl >= 0 && wh <= W - 1, o3 = hh <= H - 1 && wl >= 0, o4 = hh <= H - 1 && wh <= W - 1;
     const int i1 = o1 ? hl * W + wl : 0, i2 = o2 ? hl * W + wh : 0, i3 = o3 ? hh * W + wl : 0, i4 = o4 ? hh * W + wh : 0;
     const float* src = x + b * x_bs;
@@ -517,11 +531,11 @@ __global__ __launch_bounds__(256) void deform_backward_lds_kernel(const float* _
     const int y = p / W, xx = p - y * W, ky = tap / KW, kx = tap - ky * KW;
     const float dyo = off[b * off_bs + (long long)(2 * tap) * HW + p], dxo = off[b * off_bs + (long long)(2 * tap + 1) * HW + p];
     const float m = msk[b * msk_bs + (long long)tap * HW + p];
-    const float h = (float)(y - padH + ky) + dyo, w = (float)(xx - padW + kx) + dxo;
-    if (!(h > -1.0f && h < (float)H && w > -1.0f && w < (float)W)) continue;
-    const float fh = floorf(h), fw = floorf(w);
-    const int hl = (int)fh, wl = (int)fw, hh = hl + 1, wh = wl + 1;
-    const float lh = h - fh, lw = w - fw, uh = 1.0f - lh, uw = 1.0f - lw;
+    int hl, wl;
+    float lh, lw;
+    if (!deform_cell(y - padH + ky, dyo, H, hl, lh) || !deform_cell(xx - padW + kx, dxo, W, wl, lw)) continue;
+    const int hh = hl + 1, wh = wl + 1;
+    const float uh = 1.0f - lh, uw = 1.0f - lw;
     const bool o1 = hl >= 0 && wl >= 0, o2 = hl >= 0 && wh <= W - 1, o3 = hh <= H - 1 && wl >= 0, o4 = hh <= H - 1 && wh <= W - 1;
     const int i1 = o1 ? hl * W + wl : 0, i2 = o2 ? hl * W + wh : 0, i3 = o3 ? hh * W + wl : 0, i4 = o4 ? hh * W + wh : 0;
     const float* dc = dcols + ((long long)b * T * C + (long long)tap * C + c_begin) * HW + p;
@@ -599,15 +613,19 @@ extern "C" int accflow_convex_upsample_backward_f32(const float* dup, const floa
   ACCFLOW_RETURN_LAUNCH_STATUS();
 }
 
-extern "C" int accflow_conv_wgrad_f32(const float* x, long long x_bs, const float* dy, long long dy_bs, float* dw, float* db, int B,
-                                      int Cin, int Cout, int H, int W, int KH, int KW, int stride, int padH, int padW,
-                                      void* stream) {
-  if (!x || !dy || !dw || B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || KH <= 0 || KW <= 0 || stride <= 0) return 1;
+// Every decision of the weight-gradient launch - kernel, operand terms, grid, pixel parts - as ONE host function: the launcher
+// below runs what it returns, accflow_conv_wgrad_plan reports it (tests pin their cases to a route through it).  No device call.
+struct wgrad_plan {
+  int kernel, terms, OH, OW;          // kernel: ACCFLOW_WGRAD_GENERAL / _FAST128 / _FAST64
+  unsigned gx, gy, gz;
+  long long per, nsteps;              // steps of 16 pixels per part (as the kernels derive it from gridDim.z) / in all
+};
+static int conv_wgrad_plan(int B, int Cin, int Cout, int H, int W, int KH, int KW, int stride, int padH, int padW, long long x_bs,
+                           long long dy_bs, wgrad_plan* pl) {
+  if (B <= 0 || Cin <= 0 || Cout <= 0 || H <= 0 || W <= 0 || KH <= 0 || KW <= 0 || stride <= 0) return 1;
   const int OH = (H + 2 * padH - KH) / stride + 1, OW = (W + 2 * padW - KW) / stride + 1;
   if (OH <= 0 || OW <= 0) return 1;
   const int J = Cin * KH * KW;
-  hipMemsetAsync(dw, 0, (size_t)Cout * J * sizeof(float), as_stream(stream));
-  if (db) hipMemsetAsync(db, 0, (size_t)Cout * sizeof(float), as_stream(stream));
   const long long Ptot = (long long)B * OH * OW, nsteps = (Ptot + 15) / 16;
   // (layers of <= 64 output channels on the fast kernel's 64 x 256 tile, ACCFLOW_WGRAD_R64=0: the 128 x 128 tile everywhere)
   static const bool r64_on = [] { const char* e = getenv("ACCFLOW_WGRAD_R64"); return !e || atoi(e) != 0; }();
@@ -638,9 +656,44 @@ extern "C" int accflow_conv_wgrad_f32(const float* x, long long x_bs, const floa
   // mantissa bits per operand: passes the same gradient tests - 1e-5 of the gradient's RMS - but measured no shorter step:
   // the training step is not bound by this kernel's matrix work)
   static const int terms = [] { const char* e = getenv("ACCFLOW_WGRAD_TERMS"); return e ? atoi(e) : 3; }();
-  const dim3 grid(r64 ? cdiv(J, 256) : cdiv(J, 128), r64 ? 1 : cdiv(Cout, 128), (unsigned)Z);
-  if (r64) {
-    if (terms >= 3)
+  pl->kernel = r64 ? ACCFLOW_WGRAD_FAST64 : (fast ? ACCFLOW_WGRAD_FAST128 : ACCFLOW_WGRAD_GENERAL);
+  pl->terms = terms >= 3 ? 3 : 2;
+  pl->OH = OH;
+  pl->OW = OW;
+  pl->gx = r64 ? cdiv(J, 256) : cdiv(J, 128);
+  pl->gy = r64 ? 1 : cdiv(Cout, 128);
+  pl->gz = (unsigned)Z;
+  pl->per = (nsteps + Z - 1) / Z;
+  pl->nsteps = nsteps;
+  return 0;
+}
+
+extern "C" int accflow_conv_wgrad_plan(int B, int Cin, int Cout, int H, int W, int KH, int KW, int stride, int padH, int padW,
+                                       long long x_bs, long long dy_bs, int* out, int n) {
+  wgrad_plan pl;
+  if (!out || n < 7 || conv_wgrad_plan(B, Cin, Cout, H, W, KH, KW, stride, padH, padW, x_bs, dy_bs, &pl)) return 1;
+  const long long imax = 0x7fffffff;
+  out[0] = pl.kernel;
+  out[1] = pl.terms;
+  out[2] = (int)pl.gx;
+  out[3] = (int)pl.gy;
+  out[4] = (int)pl.gz;
+  out[5] = (int)(pl.per < imax ? pl.per : imax);
+  out[6] = (int)(pl.nsteps < imax ? pl.nsteps : imax);
+  return 0;
+}
+
+extern "C" int accflow_conv_wgrad_f32(const float* x, long long x_bs, const float* dy, long long dy_bs, float* dw, float* db, int B,
+                                      int Cin, int Cout, int H, int W, int KH, int KW, int stride, int padH, int padW,
+                                      void* stream) {
+  wgrad_plan pl;
+  if (!x || !dy || !dw || conv_wgrad_plan(B, Cin, Cout, H, W, KH, KW, stride, padH, padW, x_bs, dy_bs, &pl)) return 1;
+  const int OH = pl.OH, OW = pl.OW;
+  hipMemsetAsync(dw, 0, (size_t)Cout * Cin * KH * KW * sizeof(float), as_stream(stream));
+  if (db) hipMemsetAsync(db, 0, (size_t)Cout * sizeof(float), as_stream(stream));
+  const dim3 grid(pl.gx, pl.gy, pl.gz);
+  if (pl.kernel == ACCFLOW_WGRAD_FAST64) {
+    if (pl.terms >= 3)
       hipLaunchKernelGGL((conv_wgrad_mfma_fast_kernel<3, true>), grid, dim3(256), 0, as_stream(stream), x, x_bs, dy, dy_bs, dw, db, B,
                          Cin, Cout, H, W, OH, OW, KH, KW, padH, padW);
     else
@@ -648,8 +701,8 @@ extern "C" int accflow_conv_wgrad_f32(const float* x, long long x_bs, const floa
                          Cin, Cout, H, W, OH, OW, KH, KW, padH, padW);
     ACCFLOW_RETURN_LAUNCH_STATUS();
   }
-  if (fast) {
-    if (terms >= 3)
+  if (pl.kernel == ACCFLOW_WGRAD_FAST128) {
+    if (pl.terms >= 3)
       hipLaunchKernelGGL((conv_wgrad_mfma_fast_kernel<3>), grid, dim3(256), 0, as_stream(stream), x, x_bs, dy, dy_bs, dw, db, B, Cin,
                          Cout, H, W, OH, OW, KH, KW, padH, padW);
     else
@@ -657,7 +710,7 @@ extern "C" int accflow_conv_wgrad_f32(const float* x, long long x_bs, const floa
                          Cout, H, W, OH, OW, KH, KW, padH, padW);
     ACCFLOW_RETURN_LAUNCH_STATUS();
   }
-  if (terms >= 3)
+  if (pl.terms >= 3)
     hipLaunchKernelGGL((conv_wgrad_mfma_kernel<3>), grid, dim3(256), 0, as_stream(stream), x, x_bs, dy, dy_bs, dw, db, B, Cin, Cout, H,
                        W, OH, OW, KH, KW, stride, padH, padW);
   else

@@ -734,6 +734,17 @@ int accflow_convex_upsample_backward_f32(const float* dup, const float* flow, co
  * atomics over the pixel-axis parts: the summation order is not fixed) */
 int accflow_conv_wgrad_f32(const float* x, long long x_bs, const float* dy, long long dy_bs, float* dw, float* db, int B, int Cin,
                            int Cout, int H, int W, int KH, int KW, int stride, int padH, int padW, void* stream);
+/* What accflow_conv_wgrad_f32 would launch for these arguments: host arithmetic only (the function the launcher itself runs),
+ * no device call.  out[0] = kernel (below), out[1] = bf16 terms per operand, out[2..4] = grid x / y / z (z = parts along the pixel
+ * axis), out[5] = steps of 16 pixels per part (part z covers steps [z out[5], min((z + 1) out[5], out[6])); trailing parts may be
+ * empty), out[6] = steps in all.  Returns 1 where the launch would (shape refused), for out == NULL and for n < 7. */
+enum {
+  ACCFLOW_WGRAD_GENERAL = 0, /* any stride / padding: 128 x 128 tile, per-element gather where a chunk leaves its row */
+  ACCFLOW_WGRAD_FAST128 = 1, /* stride 1, OW == W, W % 8 == 0, |kx - padW| <= 1, tensors < 2^31 bytes: branch-free gather */
+  ACCFLOW_WGRAD_FAST64 = 2   /* the same for Cout <= 64: 64 (Cout) x 256 (Cin KH KW) tile */
+};
+int accflow_conv_wgrad_plan(int B, int Cin, int Cout, int H, int W, int KH, int KW, int stride, int padH, int padW, long long x_bs,
+                            long long dy_bs, int* out, int n);
 /* Modulated deformable convolution (torchvision.ops.deform_conv2d, AccFlow_.py:104), backward from the gradient of its deformed
  * columns dcols (B, KH*KW*C, H, W) = W^T dY: dx (B, C, H, W; zeroed here, float atomics), doffset (B, 2*KH*KW, H, W; channel 2t =
  * d/d(dy_t), 2t+1 = d/d(dx_t)), ddmask (B, KH*KW, H, W).  x / offset / dmask = the forward inputs. */
