@@ -423,8 +423,10 @@ __global__ __launch_bounds__(256, (KT == 5 ? ACCFLOW_DIRECT_KT_WAVES : 2)) void 
         const bool oka = ina && ca + q < d.C0, okb = inb && cb + q < d.C0;
         const float ma = Nrm[2 * min(ca + q, d.C0 - 1)], ra = Nrm[2 * min(ca + q, d.C0 - 1) + 1];
         const float mb = Nrm[2 * min(cb + q, d.C0 - 1)], rb = Nrm[2 * min(cb + q, d.C0 - 1) + 1];
-        xa[q] = oka ? fmaxf((xa[q] - ma) * ra, 0.0f) : 0.0f;
-        xb[q] = okb ? fmaxf((xb[q] - mb) * rb, 0.0f) : 0.0f;
+        // (a select, not fmaxf: fmaxf(NaN, 0) is 0, and a NaN must reach the range check below)
+        const float ta = (xa[q] - ma) * ra, tb = (xb[q] - mb) * rb;
+        xa[q] = oka ? (ta <= 0.0f ? 0.0f : ta) : 0.0f;
+        xb[q] = okb ? (tb <= 0.0f ? 0.0f : tb) : 0.0f;
       }
     }
     u32x4 terms[NT];

@@ -391,8 +391,9 @@ def plan_descriptor(row):
     d.act = {"store": 0, "res_relu": 1, "gru_zr": 2, "gru_q": 3, "accum": 0}[row.epi]
     d.wsplit = DUMMY if has_split else None
     if row.s16 or row.out16:       # ops._FORM_S16
-        assert f16 and has_patch
-        d.wpatch = d.wpatch16 = d.wscale16 = DUMMY
+        assert f16 and (has_patch or has_split16)      # (without the patch pack: the stem with an S16 copy)
+        d.wpatch = d.wpatch16 = DUMMY if has_patch else None
+        d.wscale16 = DUMMY
         d.wsplit16 = DUMMY if has_split16 else None
         if row.out16:
             d.out16, d.out16_bs = DUMMY, words(row.n_out, OH, OW)
