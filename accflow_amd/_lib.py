@@ -138,6 +138,9 @@ SIGNATURES = {
     "accflow_flow_to_rgb_u8": [c_f, c_ll, c_f, ctypes.c_float, c_f, c_ll, c_i, c_i, c_i, c_i, c_i, c_f],
     "accflow_frames_from_u8": [c_f, c_ll, c_ll, c_ll, c_i, c_i, c_i, c_f, c_ll, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f],
     "accflow_flow_export": [c_f, c_ll, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_ll, c_i, ctypes.c_float, c_i, c_i, c_f],
+    "accflow_frames_from_u8_resized": [c_f, c_ll, c_ll, c_ll, c_i, c_i, c_i, c_f, c_ll, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
+                                       c_i, c_f],
+    "accflow_flow_resize": [c_f, c_ll, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_ll, c_i, ctypes.c_float, c_i, c_i, c_f],
     "accflow_instance_norm_f32": [c_f, c_f, c_f, c_i, c_i, c_i, ctypes.c_float, c_i, c_f],
     "accflow_split_tanh_relu_f32": [c_f, c_f, c_ll, c_f, c_ll, c_i, c_i, c_i, c_i, c_f],
     "accflow_split_tanh_relu_idx_f32": [c_f, c_i, ctypes.POINTER(c_i), c_f, c_ll, c_f, c_ll, c_i, c_i, c_i, c_i, c_f],

@@ -180,6 +180,58 @@ class CVO(data.Dataset):
         return len(self.sampler)
 
 
+class High_Speed_Sintel(data.Dataset):
+    """data/dataset.py:164-220: one sample per folder of data_dir (sorted, minus `blacklist`), each holding
+        2_imgs/   the two original Sintel frames        43_imgs/  the high-speed frames between them (both ends included)
+        *.flo     the flow from the first original frame to the second        *.png  the occlusion mask (255 = occluded)
+    The sample dict: "gt_flow" (2,H,W), "occ_mask" (1,H,W) in 0..1, "sintel_imgs" [img1, img2] float (3,H,W) in 0..255 - as
+    in the reference - and "hs_sintel_u8": every interv-th high-speed frame as DECODED uint8 (H0,W0,3), not resized: the
+    reference's cv2.resize(img, (1024, 436)) on the host ("hs_sintel_imgs") is frames.FrameScaler.ingest's resampling on
+    the device here.  interv must divide the number of high-speed frames - 1, so that both end frames are among the chosen.
+    Files are read with frames.read_image / read_flo (PNG and PPM; a JPEG raises read_image's error)."""
+
+    def __init__(self, data_dir, interv, blacklist=[]):
+        super().__init__()
+        self.data_dir, self.interv = data_dir, int(interv)
+        if self.interv < 1:
+            raise ValueError("High_Speed_Sintel: interv must be a positive integer, got %r" % (interv,))
+        self.sample_list = [os.path.join(data_dir, x) for x in sorted(os.listdir(data_dir)) if x not in blacklist]
+
+    @staticmethod
+    def _images(folder):
+        names = sorted(os.listdir(folder))
+        return ([os.path.join(folder, n) for n in names if n.lower().endswith(".png")]
+                + [os.path.join(folder, n) for n in names if n.lower().endswith(".jpg")])
+
+    def __getitem__(self, index):
+        from ..frames import read_flo, read_image
+        root = self.sample_list[index]
+        ori, hs = self._images(os.path.join(root, "2_imgs")), self._images(os.path.join(root, "43_imgs"))
+        top = sorted(os.listdir(root))
+        flo = [n for n in top if n.lower().endswith(".flo")]
+        occ = [n for n in top if n.lower().endswith(".png")]
+        if len(ori) < 2 or not hs or not flo or not occ:
+            raise FileNotFoundError("High_Speed_Sintel: %s needs 2_imgs (2 frames), 43_imgs, a .flo and an occlusion .png" % root)
+        if (len(hs) - 1) % self.interv:
+            raise ValueError("High_Speed_Sintel: %s has %d high-speed frames; interv %d does not divide %d, so the last frame "
+                             "would be left out" % (root, len(hs), self.interv, len(hs) - 1))
+        out = {"gt_flow": totensor(read_flo(os.path.join(root, flo[0])))}
+        out["occ_mask"] = totensor(read_image(os.path.join(root, occ[0]))[..., 0:1]) / 255.0
+        out["sintel_imgs"] = [totensor(read_image(p)) for p in ori[:2]]
+        out["hs_sintel_u8"] = [torch.from_numpy(read_image(p)) for p in hs[::self.interv]]
+        return out
+
+    def __len__(self):
+        return len(self.sample_list)
+
+
+def fetch_sintel_dataloader(data_root, interv=6, batch=10, blacklist=[]):
+    """data/dataset.py:223-236."""
+    dataset = High_Speed_Sintel(data_root, interv, blacklist)
+    loader = data.DataLoader(dataset, batch_size=batch, pin_memory=False, shuffle=False, num_workers=0, drop_last=False)
+    return loader, dataset
+
+
 class _Shard(data.Sampler):
     """Per-epoch seeded permutation of the dataset, rank r of `world` takes elements r, r + world, ... of it - the same
     number on every rank (the tail that does not fill all ranks is dropped), so that the ranks of a data-parallel run

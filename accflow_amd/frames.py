@@ -4,14 +4,19 @@ A video is 8-bit interleaved frames of any size; the estimators take float32 (N,
 8.  `FramePadder.ingest` is that step as ONE launch (ops.frames_from_u8: conversion, normalisation, channel order, planar
 layout and replicate padding), where torch operators take six launches and five full-frame temporaries; its `export` is
 `unpad` plus the coding of a flow file as one launch (ops.flow_export).  Both kernels: csrc/frame_io.hip.
+`FrameScaler` puts a size policy on top - run at a working size, get the flow at the source size: its `ingest` resamples
+the frames inside that one launch (ops.frames_from_u8(size=)), its `export` resamples and rescales the flow inside the other
+(ops.flow_resize).
 
 The file formats here are the host half - standard library and numpy only, like viz.write_png: a PNG / PPM reader
 (`read_image`), Middlebury .flo (`write_flo`, `read_flo`: the reference's frame_utils.writeFlow / readFlow) and 16-bit RGB PNG
 (`write_png16`: the container of frame_utils.writeFlowKITTI and of CVO's flows).  The decoder is written to be correct, not
 fast: a video pipeline hands its decoder's buffers to `ingest` directly.
 """
+import numbers
 import struct
 import zlib
+from fractions import Fraction
 
 import numpy as np
 import torch
@@ -19,7 +24,7 @@ import torch
 from . import ops
 from .viz import _chunk
 
-__all__ = ["FramePadder", "read_image", "load_frames", "write_flo", "read_flo", "write_png16"]
+__all__ = ["FramePadder", "FrameScaler", "working_size", "read_image", "load_frames", "write_flo", "read_flo", "write_png16"]
 
 FLO_TAG = 202021.25
 
@@ -60,6 +65,96 @@ class FramePadder:
     def export(self, flow, coding="f32", scale=64.0, big_endian=False, out=None):
         """A padded flow (N,2,Hp,Wp) -> the file payload of its unpadded part (ops.flow_export)."""
         return ops.flow_export(flow, crop=self.crop, coding=coding, scale=scale, big_endian=big_endian, out=out)
+
+
+def working_size(dims, size=None, scale=None, max_side=None):
+    """The (h, w) the network should see for source frames of dims[-2:], in integer arithmetic:
+    size = (h, w): as given;  scale = s: floor(side * s + 0.5) per side, at least 8 (s is taken as the exact rational a float
+    is);  max_side = m: unchanged where the longer side is <= m, otherwise the longer side becomes m and the other
+    floor(other * m / longer + 0.5), at least 1;  none of them: the source size.  More than one of them raises."""
+    ht, wd = int(dims[-2]), int(dims[-1])
+    if ht < 1 or wd < 1:
+        raise RuntimeError("FrameScaler: frames of %d x %d" % (ht, wd))
+    if sum(a is not None for a in (size, scale, max_side)) > 1:
+        raise RuntimeError("FrameScaler: give at most one of size, scale and max_side")
+    if size is not None:
+        return ops._size2(size, "FrameScaler")
+    if scale is not None:
+        try:
+            s = Fraction(scale)
+        except (TypeError, ValueError, OverflowError):
+            s = Fraction(0)
+        if s <= 0:
+            raise RuntimeError("FrameScaler: scale must be a positive finite number, got %r" % (scale,))
+        return tuple(max(8, int((2 * side * s + 1) // 2)) for side in (ht, wd))
+    if max_side is not None:
+        if isinstance(max_side, bool) or not isinstance(max_side, numbers.Integral) or max_side < 1:
+            raise RuntimeError("FrameScaler: max_side must be a positive integer, got %r" % (max_side,))
+        m, longer = int(max_side), max(ht, wd)
+        if longer <= m:
+            return ht, wd
+        other = max(1, (2 * min(ht, wd) * m + longer) // (2 * longer))
+        return (m, other) if ht >= wd else (other, m)
+    return ht, wd
+
+
+class FrameScaler:
+    """Run at a working size, get the flow at the source size: frames of dims[-2:] are resampled to `.size` inside ingest's
+    launch and the flow is resampled back - its vectors scaled with it - inside export's.  size / scale / max_side:
+    working_size's policy (at most one).  `.padder` is the FramePadder of the working size; pad: its mode.  interp:
+    "bilinear" or "area", for the frames (a flow is always resampled bilinearly).  With no size argument - or one that
+    leaves the size as it is - every method is the FramePadder's."""
+
+    def __init__(self, dims, size=None, scale=None, max_side=None, pad="sintel", interp="bilinear"):
+        if interp not in ("bilinear", "area"):
+            raise RuntimeError("FrameScaler: interp must be 'bilinear' or 'area', got %r" % (interp,))
+        self.ht, self.wd = int(dims[-2]), int(dims[-1])
+        self.size = working_size(dims, size, scale, max_side)
+        self.interp = interp
+        self.padder = FramePadder(self.size, mode=pad)
+        self.resizes = self.size != (self.ht, self.wd)
+
+    def ingest(self, u8, layout="hwc", bgr=False, normalize=True, out=None):
+        """uint8 frames at the source size -> float32 (N,3,Hp,Wp) at the padded working size, one launch."""
+        if not self.resizes:
+            return self.padder.ingest(u8, layout=layout, bgr=bgr, normalize=normalize, out=out)
+        if isinstance(u8, torch.Tensor) and u8.dim() == 3:
+            u8 = u8[None]
+        if isinstance(u8, torch.Tensor) and u8.dim() == 4 and layout in ("hwc", "chw"):
+            hw = tuple(u8.shape[1:3]) if layout == "hwc" else tuple(u8.shape[2:4])
+            if hw != (self.ht, self.wd):
+                raise RuntimeError("FrameScaler.ingest: frames are %d x %d, the scaler was made for %d x %d" % (hw + (self.ht, self.wd)))
+        return ops.frames_from_u8(u8, layout=layout, bgr=bgr, pad=tuple(self.padder._pad), normalize=normalize, out=out,
+                                  size=self.size, interp=self.interp)
+
+    def _window(self, flow, who):
+        """(flow, crop): a padded working flow with the frame's window, or an unpadded one (made dense) with none."""
+        h, w = self.size
+        pl, pr, pt, pb = self.padder._pad
+        if isinstance(flow, torch.Tensor) and flow.dim() == 4:
+            if tuple(flow.shape[2:]) == (h + pt + pb, w + pl + pr):
+                return flow, self.padder.crop
+            if tuple(flow.shape[2:]) == (h, w):
+                return flow.contiguous(), None
+        raise RuntimeError("FrameScaler.%s: expected a (N,2,%d,%d) flow of the working size or its padded form, got %s" % (
+            who, h, w, tuple(flow.shape) if isinstance(flow, torch.Tensor) else type(flow)))
+
+    def flow(self, flow):
+        """A working-size flow - padded (N,2,Hp,Wp) as the model returns it, or unpadded (N,2,h,w) - as (N,2,H,W) at the
+        SOURCE size.  Without a resize: the padder's unpad (a view)."""
+        flow, crop = self._window(flow, "flow")
+        if not self.resizes:
+            return flow if crop is None else self.padder.unpad(flow)
+        return ops.flow_resize(flow, (self.ht, self.wd), crop=crop, coding="nchw")
+
+    def export(self, flow, coding="f32", scale=64.0, big_endian=False, out=None):
+        """A working-size flow (as in `flow`) -> the file payload at the SOURCE size, one launch."""
+        if not self.resizes:
+            return self.padder.export(flow, coding=coding, scale=scale, big_endian=big_endian, out=out)
+        if coding not in ("f32", "u16"):
+            raise RuntimeError("FrameScaler.export: coding must be 'f32' or 'u16', got %r" % (coding,))
+        flow, crop = self._window(flow, "export")
+        return ops.flow_resize(flow, (self.ht, self.wd), crop=crop, coding=coding, scale=scale, big_endian=big_endian, out=out)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1652,15 +1652,42 @@ def flow_to_rgb(flow, maxrad, clip=None, bgr=False, layout="hwc", out=None):
     return out
 
 
-def frames_from_u8(src, layout="hwc", bgr=False, pad=(0, 0, 0, 0), normalize=True, out=None):
+RESIZE_MAX_SIDE = 32768     # csrc/frame_io.hip: the resampling geometry is 32-bit integer arithmetic up to this side
+
+
+def _size2(size, who, name="size"):
+    """(h, w): two positive integers (integral floats are refused too: a size is not rounded here)."""
+    import numbers
+    try:
+        hw = tuple(size)
+        ok = len(hw) == 2 and all(isinstance(v, numbers.Integral) and not isinstance(v, bool) and v > 0 for v in hw)
+        hw = tuple(int(v) for v in hw) if ok else ()
+    except TypeError:
+        hw, ok = (), False
+    if not ok:
+        raise RuntimeError("%s: %s must be two positive integers (h, w), got %r" % (who, name, size))
+    if max(hw) > RESIZE_MAX_SIDE:
+        raise RuntimeError("%s: %s %r is beyond the largest side a resampling takes, %d" % (who, name, hw, RESIZE_MAX_SIDE))
+    return hw
+
+
+def frames_from_u8(src, layout="hwc", bgr=False, pad=(0, 0, 0, 0), normalize=True, out=None, size=None, interp="bilinear"):
     """8-bit frames -> the estimators' input in one launch: src uint8 (N,H,W,3) (layout "hwc") or (N,3,H,W) ("chw"), RGB or
     BGR -> float32 (N,3,H+t+b,W+l+r), pad = (l, r, t, b) replicated as F.pad(..., mode="replicate") does it.  normalize:
     2 * (x / 255.0) - 1 with torch's bits; otherwise the plain values 0..255.  src is taken as it is, with its byte strides:
     a pitched or sliced view (rows, planes and samples at any distance, any base address) is not made contiguous - only the
-    bytes of a row must be adjacent.  out: a float32 tensor of the result's shape with dense samples to write into."""
+    bytes of a row must be adjacent.  out: a float32 tensor of the result's shape with dense samples to write into.
+    size = (h, w): the frames are resampled to h x w inside the same launch, before the normalisation, and the RESIZED frame
+    is padded: float32 (N,3,h+t+b,w+l+r).  interp "bilinear": half-pixel centres as cv2.INTER_LINEAR and
+    F.interpolate(align_corners=False), the coordinates exact rationals (include/accflow_hip.h); "area": the integer window
+    mean of F.interpolate(mode="area").  size = (H, W) gives the bits of size = None."""
     who = "frames_from_u8"
     if layout not in ("hwc", "chw"):
         raise RuntimeError("%s: layout must be 'hwc' or 'chw', got %r" % (who, layout))
+    if interp not in ("bilinear", "area"):
+        raise RuntimeError("%s: interp must be 'bilinear' or 'area', got %r" % (who, interp))
+    if size is not None:
+        size = _size2(size, who)
     cdim = 3 if layout == "hwc" else 1
     if not (isinstance(src, torch.Tensor) and src.dim() == 4 and src.shape[cdim] == 3 and src.numel() > 0):
         raise RuntimeError("%s: src must be a non-empty %s tensor, got %s" % (
@@ -1683,7 +1710,12 @@ def frames_from_u8(src, layout="hwc", bgr=False, pad=(0, 0, 0, 0), normalize=Tru
         ok, s_row, s_plane = W == 1 or st[3] == 1, st[2], st[1]
     if not ok:
         raise RuntimeError("%s: the bytes of a row of src must be adjacent (strides %s)" % (who, st))
-    shape = (N, 3, H + pads[2] + pads[3], W + pads[0] + pads[1])
+    oh, ow = (H, W) if size is None else size
+    if size is not None and max(H, W) > RESIZE_MAX_SIDE:
+        raise RuntimeError("%s: %d x %d frames are beyond the largest side a resampling takes, %d" % (who, H, W, RESIZE_MAX_SIDE))
+    if size is not None and interp == "area" and (-(-H // oh) + 1) * (-(-W // ow) + 1) >= 1 << 24:
+        raise RuntimeError("%s: an area window of %d x %d -> %d x %d could hold 2^24 pixels or more" % (who, H, W, oh, ow))
+    shape = (N, 3, oh + pads[2] + pads[3], ow + pads[0] + pads[1])
     if out is not None and not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and tuple(out.shape) == shape):
         raise RuntimeError("%s: out must be a float32 tensor of shape %s" % (who, shape))
     if not src.is_cuda:
@@ -1692,6 +1724,12 @@ def frames_from_u8(src, layout="hwc", bgr=False, pad=(0, 0, 0, 0), normalize=Tru
     lib = _lib.load()
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=src.device)
+    if size is not None:
+        _check(lib.accflow_frames_from_u8_resized(_p(src), st[0] if N > 1 else 0, s_row if H > 1 else 0, s_plane,
+                                                  int(layout == "chw"), int(bool(bgr)), int(bool(normalize)), _p(out), obs, N, H, W,
+                                                  pads[0], pads[1], pads[2], pads[3], oh, ow, int(interp == "area"), _stream()),
+               "accflow_frames_from_u8_resized")
+        return out
     _check(lib.accflow_frames_from_u8(_p(src), st[0] if N > 1 else 0, s_row if H > 1 else 0, s_plane, int(layout == "chw"),
                                       int(bool(bgr)), int(bool(normalize)), _p(out), obs, N, H, W, pads[0], pads[1], pads[2],
                                       pads[3], _stream()), "accflow_frames_from_u8")
@@ -1737,6 +1775,51 @@ def flow_export(flow, crop=None, coding="f32", scale=64.0, big_endian=False, out
     obs = (out.stride(0) if N > 1 else 0) * out.element_size()
     _check(lib.accflow_flow_export(_p(flow), fbs, Hp, Wp, y0, x0, H, W, _p(out), obs, int(coding == "u16"), scale,
                                    int(bool(big_endian)), N, _stream()), "accflow_flow_export")
+    return out
+
+
+def flow_resize(flow, size, crop=None, coding="nchw", scale=64.0, big_endian=False, out=None):
+    """A flow at another size, in one launch: the window crop = (y0, x0, Hc, Wc) (None: everything) of flow (N,2,Hp,Wp) is
+    resampled bilinearly to size = (H, W) - half-pixel centres, the taps clamped inside the window so that padding around it
+    is never read - and its vectors are scaled with it: u by W / Wc, v by H / Hc.  The result goes out as
+      coding "nchw": float32 (N,2,H,W), a flow as every operator here takes it;
+      coding "f32" / "u16": the file payloads of flow_export, `scale` and `big_endian` as there.
+    The three codings hold the same values, and with size == (Hc, Wc) they are flow_export's.  out: as in flow_export."""
+    who = "flow_resize"
+    if coding not in ("nchw", "f32", "u16"):
+        raise RuntimeError("%s: coding must be 'nchw', 'f32' or 'u16', got %r" % (who, coding))
+    N, Hp, Wp = _flow_shape(flow, "flow", who)
+    H, W = _size2(size, who)
+    if crop is None:
+        crop = (0, 0, Hp, Wp)
+    try:
+        y0, x0, Hc, Wc = (int(c) for c in crop)
+    except (TypeError, ValueError):
+        raise RuntimeError("%s: crop must be (y0, x0, H, W), got %r" % (who, crop))
+    if not (y0 >= 0 and x0 >= 0 and Hc > 0 and Wc > 0 and y0 + Hc <= Hp and x0 + Wc <= Wp):
+        raise RuntimeError("%s: crop %r does not lie inside the %d x %d flow" % (who, tuple(crop), Hp, Wp))
+    if max(Hc, Wc) > RESIZE_MAX_SIDE:
+        raise RuntimeError("%s: a %d x %d window is beyond the largest side a resampling takes, %d" % (who, Hc, Wc, RESIZE_MAX_SIDE))
+    scale = float(scale)
+    if coding == "u16" and not (scale > 0.0 and scale < float("inf")):
+        raise RuntimeError("%s: scale must be a positive finite number, got %r" % (who, scale))
+    shape = {"nchw": (N, 2, H, W), "f32": (N, H, W, 2), "u16": (N, H, W, 3)}[coding]
+    dtypes = (torch.uint16, torch.int16) if coding == "u16" else (torch.float32,)
+    if out is not None:
+        if not (isinstance(out, torch.Tensor) and out.dtype in dtypes and tuple(out.shape) == shape):
+            raise RuntimeError("%s: out must be a %s tensor of shape %s" % (who, str(dtypes[0]).replace("torch.", ""), shape))
+        if not out[0].is_contiguous():
+            raise RuntimeError("%s: every sample of out must be dense (strides %s)" % (who, out.stride()))
+    fbs = _plane4(flow, "flow")
+    if out is not None and not out.is_cuda:
+        raise RuntimeError("%s: expected a CUDA tensor for out" % who)
+    lib = _lib.load()
+    if out is None:
+        out = torch.empty(shape, dtype=dtypes[0], device=flow.device)
+    obs = (out.stride(0) if N > 1 else 0) * out.element_size()
+    _check(lib.accflow_flow_resize(_p(flow), fbs, Hp, Wp, y0, x0, Hc, Wc, H, W, _p(out), obs,
+                                   {"f32": 0, "u16": 1, "nchw": 2}[coding], scale, int(bool(big_endian)), N, _stream()),
+           "accflow_flow_resize")
     return out
 
 

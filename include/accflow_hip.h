@@ -508,6 +508,39 @@ int accflow_frames_from_u8(const unsigned char* src, long long s_bs, long long s
 int accflow_flow_export(const float* flow, long long f_bs, int Hp, int Wp, int y0, int x0, int H, int W, void* out,
                         long long o_bs, int coding, float scale, int big_endian, int N, void* stream);
 
+/* ---- The same two ends with a resampling inside the launch (csrc/frame_io.hip) ----
+ * Geometry of both: pixel centres at half-integers (cv2.INTER_LINEAR, F.interpolate(align_corners=False)).  For output
+ * index x of n_out over n_in source samples, in integers:
+ *     num = (2x+1) n_in - n_out,  den = 2 n_out,  i0 = floor(num / den),  f = (float)(num - i0 den) / (float)den
+ * - one correctly rounded fp32 division of two exact integers, never a float product of a coordinate.  The taps are
+ * clamp(i0) and clamp(i0 + 1), clamped into the source (or the crop window), and a blend is
+ *     lerp(f, a, b) = f == 0 ? a : a + f (b - a),       every operation rounded to fp32 on its own,
+ * along x first, then along y: a resize to the same size is the identity bit for bit, even next to a NaN.
+ * Every side - source, window and output - is at most 32768, which keeps the integers above within 32 bits.
+ *
+ * Frames.  accflow_frames_from_u8 with (H,W) resampled to (out_h,out_w) before the replicate padding, which pads the RESIZED
+ * frame: out is float32 (N,3,out_h+pad_t+pad_b,out_w+pad_l+pad_r),
+ *     out[n,c,y,x] = g(R[n, clamp(y - pad_t, 0, out_h-1), clamp(x - pad_l, 0, out_w-1), bgr ? 2 - c : c]),
+ * g as above applied to the resampled level R (a float in [0, 255]), and
+ *   interp 0, bilinear: R = lerp(fy, lerp(fx, s00, s01), lerp(fx, s10, s11)) on the byte values as fp32;
+ *   interp 1, area    : R = (float)sum / (float)count over the rows floor(y H / out_h) .. ceil((y+1) H / out_h) - 1 and the
+ *                       columns likewise (the window of F.interpolate(mode="area")), the bytes summed as integers; refused
+ *                       where a window could hold 2^24 pixels or more.
+ * A thread takes 4 output pixels of a row and stores 16 bytes per channel; the source is read as bytes. */
+int accflow_frames_from_u8_resized(const unsigned char* src, long long s_bs, long long s_row, long long s_plane, int planar,
+                                   int bgr, int normalize, float* out, long long o_bs, int N, int H, int W, int pad_l, int pad_r,
+                                   int pad_t, int pad_b, int out_h, int out_w, int interp, void* stream);
+
+/* Flows.  The crop window (y0,x0,Hc,Wc) of flow (N,2,Hp,Wp) resampled bilinearly to (H,W), the taps clamped INSIDE the
+ * window (the padding around it is never read), and the vectors scaled to the new size:
+ *     u' = lerp(...) * ((float)W / (float)Wc),   v' = lerp(...) * ((float)H / (float)Hc)      (one fp32 multiply each).
+ * out, o_bs, scale and big_endian as in accflow_flow_export;
+ *   coding 0: float32 (N,H,W,2) interleaved;   coding 1: uint16 (N,H,W,3) codes;   coding 2: float32 (N,2,H,W) planar.
+ * The three codings store the same resampled value, and with (H,W) == (Hc,Wc) codings 0 and 1 are accflow_flow_export's
+ * bytes. */
+int accflow_flow_resize(const float* flow, long long f_bs, int Hp, int Wp, int y0, int x0, int Hc, int Wc, int H, int W,
+                        void* out, long long o_bs, int coding, float scale, int big_endian, int N, void* stream);
+
 /* InstanceNorm2d (no affine, eps, biased var; extractor.py:36-39) over each (b,c) plane of `x`,
  * fused with what follows it in ResidualBlock.forward (extractor.py:56-63):
  *   mode 0: out = norm(x)                    (downsample branch)
