@@ -85,7 +85,6 @@ __global__ __launch_bounds__(256) void conv2d_bf16s_kernel(const accflow_conv_de
   float xr[XPT];
   u32x4 wr[WPT];
   bool bad = false;
-  constexpr float ASC = (float)(1 << ACCFLOW_F16_ASHIFT);
   f32x16 acc[TC][TP];
 #pragma unroll
   for (int tc = 0; tc < TC; ++tc)
@@ -108,11 +107,11 @@ __global__ __launch_bounds__(256) void conv2d_bf16s_kernel(const accflow_conv_de
   do {                                                                                            \
     {                                                                                             \
       u32x4 terms[NT];                                                                            \
-      if constexpr (F16) split8_f16<0>(xr, terms, bad, ASC);                                      \
+      if constexpr (F16) s16_split8(xr, terms[0], terms[1], bad);                                 \
       else split8_bf16<NT, 0>(xr, terms);                                                         \
       _Pragma("unroll") for (int t = 0; t < NT; ++t) Xs[BUF][t][kg * OPT][px_local] = terms[t];   \
       if constexpr (OPT == 2) {                                                                   \
-        if constexpr (F16) split8_f16<8 * (OPT - 1)>(xr, terms, bad, ASC);                        \
+        if constexpr (F16) s16_split8<8 * (OPT - 1)>(xr, terms[0], terms[1], bad);                \
         else split8_bf16<NT, 8 * (OPT - 1)>(xr, terms);                                           \
         _Pragma("unroll") for (int t = 0; t < NT; ++t) Xs[BUF][t][kg * OPT + 1][px_local] = terms[t]; \
       }                                                                                           \

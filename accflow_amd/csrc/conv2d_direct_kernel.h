@@ -117,8 +117,6 @@ template <bool F16, class PixMap>
 __device__ __forceinline__ void conv_epilogue_tapgemm(const accflow_conv_desc& d, f32x16 (&acc)[1][4], int cblk0, int wave,
                                                       int lane, int tid, int OHW, PixMap pixmap, float* red) {
   typedef float f32x4_ __attribute__((ext_vector_type(4)));
-  typedef float f32x2_ __attribute__((ext_vector_type(2)));
-  typedef _Float16 f16x2_ __attribute__((ext_vector_type(2)));
   const int l31 = lane & 31, kh = lane >> 5, lh4 = kh * 4;
   const int rowbase = cblk0 + wave * 32;
   const int R = d.tg_rows;
@@ -144,7 +142,6 @@ __device__ __forceinline__ void conv_epilogue_tapgemm(const accflow_conv_desc& d
     for (int t = 0; t < 2; ++t)
       a2[s][t] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(
                                                r_w2, (int)av2, (int)(unsigned)(t * term_bytes2 + ((rowbase >> 4) + s) * step_bytes2), 0));
-  constexpr float ASC16 = (float)(1 << ACCFLOW_F16_ASHIFT);
   bool bad16 = false;
 #pragma unroll
   for (int tp = 0; tp < 4; ++tp) {
@@ -159,16 +156,10 @@ __device__ __forceinline__ void conv_epilogue_tapgemm(const accflow_conv_desc& d
         const int m = 2 * s + (e2 >> 1), q = (2 * e2) & 3;
         float va = fmaf(acc[0][tp][4 * m + q], sv[m][q], bv[m][q]) + 0.0f;
         float vb = fmaf(acc[0][tp][4 * m + q + 1], sv[m][q + 1], bv[m][q + 1]) + 0.0f;
-        va = fmaxf(va, 0.0f) * ASC16;
-        vb = fmaxf(vb, 0.0f) * ASC16;
-        bad16 |= !(va < 65520.0f) | !(vb < 65520.0f);
-        const f32x2_ v2 = {va, vb};
-        const f16x2_ hq = __builtin_convertvector(v2, f16x2_);
-        const f32x2_ back = __builtin_convertvector(hq, f32x2_);
-        const f32x2_ rest = {va - back[0], vb - back[1]};
-        const f16x2_ lq = __builtin_convertvector(rest, f16x2_);
-        hi[e2] = __builtin_bit_cast(unsigned, hq);
-        lo[e2] = __builtin_bit_cast(unsigned, lq);
+        va = fmaxf(va, 0.0f) * S16_SCALE;
+        vb = fmaxf(vb, 0.0f) * S16_SCALE;
+        bad16 |= !(va < S16_LIMIT) | !(vb < S16_LIMIT);     // (s16_bad2 without the fabsf: after the ReLU)
+        s16_split2(va, vb, hi[e2], lo[e2]);
       }
       const u32x4 hv = {hi[0], hi[1], hi[2], hi[3]}, lv = {lo[0], lo[1], lo[2], lo[3]};
       const bf16x8 bh = __builtin_bit_cast(bf16x8, hv), bl = __builtin_bit_cast(bf16x8, lv);
@@ -409,7 +400,6 @@ __global__ __launch_bounds__(256, (KT == 5 ? ACCFLOW_DIRECT_KT_WAVES : 2)) void 
     }
   };
   bool bad = false;  // F16: an activation outside the scaled fp16 range was seen
-  constexpr float ASC = (float)(1 << ACCFLOW_F16_ASHIFT);
   if constexpr (NORM) {
     for (int i = tid; i < 2 * d.C0; i += 256) Nrm[i] = d.in_norm[(long long)tb * 2 * d.C0 + i];
     __syncthreads();
@@ -430,13 +420,13 @@ __global__ __launch_bounds__(256, (KT == 5 ? ACCFLOW_DIRECT_KT_WAVES : 2)) void 
       }
     }
     u32x4 terms[NT];
-    if constexpr (F16) split8_f16<0>(xa, terms, bad, ASC);
+    if constexpr (F16) s16_split8(xa, terms[0], terms[1], bad);
     else split8_bf16<NT, 0>(xa, terms);
     if (p_pix[0] >= 0) {
 #pragma unroll
       for (int t = 0; t < NT; ++t) Pst[stage * PSTAGE + t * (OCT * DIR_NPMAX) + p_oct[0] * NPS + p_pix[0]] = terms[t];
     }
-    if constexpr (F16) split8_f16<0>(xb, terms, bad, ASC);
+    if constexpr (F16) s16_split8(xb, terms[0], terms[1], bad);
     else split8_bf16<NT, 0>(xb, terms);
     if (p_pix[1] >= 0) {
 #pragma unroll

@@ -1,6 +1,7 @@
 // Device code shared by the convolution translation units (conv_small.hip: the <= 4-output-channel kernels; conv_pack.hip:
 // the weight / operand packs; conv2d_f32.hip: fp32-MFMA im2col kernel; conv2d_bf16s.hip: split-bf16 im2col kernel +
-// displaced correlation store; conv2d_direct.hip: split-bf16 direct-A patch kernel).  Everything here is internal linkage.
+// displaced correlation store; conv2d_direct.hip: split-bf16 direct-A patch kernel; conv_ksplit.hip: its split-K reduction; corr_gemm.hip, gma_attn.hip:
+// the register / LDS-ring GEMMs of the correlation volume and the GMA attention).  Everything here is internal linkage.
 // The dispatch itself is host code without a HIP header: conv_plan.h / conv_plan.cpp, on the tile constants of
 // conv_tiles.h; conv2d.hip runs it and calls the launchers of launchers.h.
 #pragma once
@@ -188,8 +189,6 @@ __device__ __forceinline__ void conv_epilogue_impl(const accflow_conv_desc& d, f
   float h[NS][TP], z[NS][TP], pa[NS][TP];
   float s16v[TP][4];
   bool bad16 = false;
-  typedef float f32x2_ __attribute__((ext_vector_type(2)));
-  typedef _Float16 f16x2_ __attribute__((ext_vector_type(2)));
   typedef unsigned u32x2_ __attribute__((ext_vector_type(2)));
 #pragma unroll
   for (int i = 0; i < NS; ++i)
@@ -292,22 +291,15 @@ __device__ __forceinline__ void conv_epilogue_impl(const accflow_conv_desc& d, f
       if (cs0 >= 0 && oct < O16) {                           // (wave-uniform)
         const int nvalid = n16 - (cs0 + lh4);                // channels of this lane's group that exist
         const bool full = (oct + 1) * 8 <= n16;              // (wave-uniform) every channel of the octet exists
-        constexpr float ASC16 = (float)(1 << ACCFLOW_F16_ASHIFT);
 #pragma unroll
         for (int tp = 0; tp < TP; ++tp) {
           unsigned hi2[2], lo2[2];
 #pragma unroll
           for (int k = 0; k < 2; ++k) {
-            const float a = (2 * k < nvalid) ? s16v[tp][2 * k] * ASC16 : 0.0f;
-            const float b = (2 * k + 1 < nvalid) ? s16v[tp][2 * k + 1] * ASC16 : 0.0f;
-            bad16 |= !(fabsf(a) < 65520.0f) | !(fabsf(b) < 65520.0f);
-            const f32x2_ v2 = {a, b};
-            const f16x2_ hq = __builtin_convertvector(v2, f16x2_);
-            const f32x2_ back = __builtin_convertvector(hq, f32x2_);
-            const f32x2_ rest = {a - back[0], b - back[1]};
-            const f16x2_ lq = __builtin_convertvector(rest, f16x2_);
-            hi2[k] = __builtin_bit_cast(unsigned, hq);
-            lo2[k] = __builtin_bit_cast(unsigned, lq);
+            const float a = (2 * k < nvalid) ? s16v[tp][2 * k] * S16_SCALE : 0.0f;
+            const float b = (2 * k + 1 < nvalid) ? s16v[tp][2 * k + 1] * S16_SCALE : 0.0f;
+            bad16 |= s16_bad2(a, b);
+            s16_split2(a, b, hi2[k], lo2[k]);
           }
           // byte offset of the octet's hi plane; lo plane + OHW * 16 (channel blocks: block, then the octet inside it)
           const int so = cb ? (int)(unsigned)(((long long)(cs0 / cb) * d.out16_cbs) * 4 + ((cs0 % cb) >> 3) * 2 * OHW * 16)
@@ -387,10 +379,7 @@ __device__ __forceinline__ void conv_epilogue_lean(const accflow_conv_desc& d, f
     }
   const bool no_scale = d.wscale16 == nullptr;
   bool bad16 = false;
-  typedef float f32x2_ __attribute__((ext_vector_type(2)));
-  typedef _Float16 f16x2_ __attribute__((ext_vector_type(2)));
   typedef unsigned u32x2_ __attribute__((ext_vector_type(2)));
-  constexpr float ASC16 = (float)(1 << ACCFLOW_F16_ASHIFT);
 #pragma unroll
   for (int tc = 0; tc < TC; ++tc)
 #pragma unroll
@@ -427,15 +416,9 @@ __device__ __forceinline__ void conv_epilogue_lean(const accflow_conv_desc& d, f
           unsigned hi2[2], lo2[2];
 #pragma unroll
           for (int k = 0; k < 2; ++k) {
-            const float a = o[tp][2 * k] * ASC16, b = o[tp][2 * k + 1] * ASC16;
-            bad16 |= !(fabsf(a) < 65520.0f) | !(fabsf(b) < 65520.0f);
-            const f32x2_ v2 = {a, b};
-            const f16x2_ hq = __builtin_convertvector(v2, f16x2_);
-            const f32x2_ back = __builtin_convertvector(hq, f32x2_);
-            const f32x2_ rest = {a - back[0], b - back[1]};
-            const f16x2_ lq = __builtin_convertvector(rest, f16x2_);
-            hi2[k] = __builtin_bit_cast(unsigned, hq);
-            lo2[k] = __builtin_bit_cast(unsigned, lq);
+            const float a = o[tp][2 * k] * S16_SCALE, b = o[tp][2 * k + 1] * S16_SCALE;
+            bad16 |= s16_bad2(a, b);
+            s16_split2(a, b, hi2[k], lo2[k]);
           }
           const u32x2_ hv = {hi2[0], hi2[1]}, lv = {lo2[0], lo2[1]};
 #ifndef ACCFLOW_KPROF_NOSTORE
@@ -466,8 +449,6 @@ __device__ __forceinline__ void conv_epilogue_gru16(const accflow_conv_desc& d, 
   constexpr unsigned MASKED = 0xFFFFFFFFu;
   constexpr int TPH = 2;
   typedef float f32x4_ __attribute__((ext_vector_type(4)));
-  typedef float f32x2_ __attribute__((ext_vector_type(2)));
-  typedef _Float16 f16x2_ __attribute__((ext_vector_type(2)));
   typedef unsigned u32x2_ __attribute__((ext_vector_type(2)));
   typedef unsigned u32x4_ __attribute__((ext_vector_type(4)));
   const int l31 = lane & 31, lh4 = (lane >> 5) * 4;
@@ -488,7 +469,6 @@ __device__ __forceinline__ void conv_epilogue_gru16(const accflow_conv_desc& d, 
   const __amdgpu_buffer_rsrc_t r_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(d.bias ? d.bias : d.wscale16), 0,
                                                                       d.bias ? d.Cout * 4 : 0, 0x00020000);
   const __amdgpu_buffer_rsrc_t r_s = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(d.wscale16), 0, d.CoutPad * 4, 0x00020000);
-  constexpr float ASC16 = (float)(1 << ACCFLOW_F16_ASHIFT);
   bool bad16 = false;
 #pragma unroll
   for (int hh = 0; hh < TP / TPH; ++hh) {
@@ -535,9 +515,7 @@ __device__ __forceinline__ void conv_epilogue_gru16(const accflow_conv_desc& d, 
           const float v = apply_act(fmaf(acc[0][tp][4 * m + q], sv[S][q], bv[S][q]) + pre[S][t][q],   // (no bias: an empty range reads 0)
                                     ZR ? ACCFLOW_ACT_SIGMOID : ACCFLOW_ACT_TANH);
           if (need_h) {
-            const unsigned wh = hhi[S][t][q >> 1], wl = hlo[S][t][q >> 1];
-            const unsigned short hq = (unsigned short)((q & 1) ? wh >> 16 : wh & 0xFFFFu), lq = (unsigned short)((q & 1) ? wl >> 16 : wl & 0xFFFFu);
-            const float hv = ((float)__builtin_bit_cast(_Float16, hq) + (float)__builtin_bit_cast(_Float16, lq)) * (1.0f / ASC16);
+            const float hv = s16_join(hhi[S][t][q >> 1], hlo[S][t][q >> 1], q & 1);
             o[q] = ZR ? v * hv : gru_blend(zz[S][t][q], hv, v);
           } else {
             o[q] = v;
@@ -551,15 +529,9 @@ __device__ __forceinline__ void conv_epilogue_gru16(const accflow_conv_desc& d, 
           unsigned hi2[2], lo2[2];
 #pragma unroll
           for (int k = 0; k < 2; ++k) {
-            const float a = o[2 * k] * ASC16, b2 = o[2 * k + 1] * ASC16;
-            bad16 |= !(fabsf(a) < 65520.0f) | !(fabsf(b2) < 65520.0f);
-            const f32x2_ v2 = {a, b2};
-            const f16x2_ hq2 = __builtin_convertvector(v2, f16x2_);
-            const f32x2_ back = __builtin_convertvector(hq2, f32x2_);
-            const f32x2_ rest = {a - back[0], b2 - back[1]};
-            const f16x2_ lq2 = __builtin_convertvector(rest, f16x2_);
-            hi2[k] = __builtin_bit_cast(unsigned, hq2);
-            lo2[k] = __builtin_bit_cast(unsigned, lq2);
+            const float a = o[2 * k] * S16_SCALE, b2 = o[2 * k + 1] * S16_SCALE;
+            bad16 |= s16_bad2(a, b2);
+            s16_split2(a, b2, hi2[k], lo2[k]);
           }
           const u32x2_ hv2 = {hi2[0], hi2[1]}, lv2 = {lo2[0], lo2[1]};
           const int so16 = ((cst + 8 * m) >> 3) * 2 * OHW * 16;
@@ -647,28 +619,6 @@ typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-
-// hi + lo fp16 split of 8 floats times the power of two `s` (round to nearest each); bad |= a scaled value outside
-// fp16's range (or NaN)
-template <int OFF, int N>
-__device__ __forceinline__ void split8_f16(const float (&x)[N], u32x4 (&out)[2], bool& bad, float s) {
-  unsigned hi[4], lo[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const float a = x[OFF + 2 * j] * s, b = x[OFF + 2 * j + 1] * s;
-    bad |= !(fabsf(a) < 65520.0f) | !(fabsf(b) < 65520.0f);
-    const f32x2 v = {a, b};
-    const f16x2 h = __builtin_convertvector(v, f16x2);
-    const f32x2 back = __builtin_convertvector(h, f32x2);
-    const f32x2 r = {a - back[0], b - back[1]};
-    const f16x2 l = __builtin_convertvector(r, f16x2);
-    hi[j] = __builtin_bit_cast(unsigned, h);
-    lo[j] = __builtin_bit_cast(unsigned, l);
-  }
-  { u32x4 v4 = {hi[0], hi[1], hi[2], hi[3]}; out[0] = v4; }
-  { u32x4 v4 = {lo[0], lo[1], lo[2], lo[3]}; out[1] = v4; }
-}
 
 template <int NT, int OFF, int N>
 __device__ __forceinline__ void split8_bf16(const float (&x)[N], u32x4 (&out)[NT]) {

@@ -79,7 +79,7 @@ __global__ __launch_bounds__(256) void conv_pack_kmajor_kernel(const float* __re
   if (f16) {
     u32x4 t2[2];
     bool bad = false;
-    split8_f16<0>(x, t2, bad, 1.0f);  // (cscale already carries 2^ACCFLOW_F16_ASHIFT)
+    s16_split8(x, t2[0], t2[1], bad, 1.0f);  // (cscale already carries 2^ACCFLOW_F16_ASHIFT)
     if (bad && guard) atomicOr(guard, 1);
     ws[idx] = t2[0];
     ws[per_term + idx] = t2[1];

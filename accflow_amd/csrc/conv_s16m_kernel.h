@@ -120,12 +120,9 @@ __device__ __forceinline__ void conv_epilogue_lean_res(const accflow_conv_desc& 
                       : (unsigned)((b * d.e0_bs + (long long)rem + (long long)lh4 * OHW) * 4);
   }
   typedef float f32x4_ __attribute__((ext_vector_type(4)));
-  typedef float f32x2_ __attribute__((ext_vector_type(2)));
-  typedef _Float16 f16x2_ __attribute__((ext_vector_type(2)));
   typedef unsigned u32x2_ __attribute__((ext_vector_type(2)));
   const bool no_scale = d.wscale16 == nullptr;
   bool bad16 = false;
-  constexpr float ASC16 = (float)(1 << ACCFLOW_F16_ASHIFT);
   // scale / bias of all rows first (8 vector loads per 32 rows), then the residual operand one 4-row group ahead of the
   // stores (2 x 4 * TP registers: the kernel's register count must stay the main loop's)
   f32x4_ bv[TC][4], sv[TC][4];
@@ -138,15 +135,14 @@ __device__ __forceinline__ void conv_epilogue_lean_res(const accflow_conv_desc& 
       sv[tc][m] = __builtin_bit_cast(f32x4_, __builtin_amdgcn_raw_buffer_load_b128(r_s, off, 0, 0));
     }
   float e[2][TP][4];
-  typedef _Float16 f16x4_ __attribute__((ext_vector_type(4)));
 #define LEAN_FETCH(G, E)                                                                                          \
   do {                                                                                                            \
     if constexpr (E16) {                                                                                          \
       const int so16_ = ((rowbase + ((G) >> 2) * 32 + 8 * ((G) & 3)) >> 3) * 2 * OHW * 16;                        \
       _Pragma("unroll") for (int tp = 0; tp < TP; ++tp) {                                                         \
-        const f16x4_ h_ = __builtin_bit_cast(f16x4_, __builtin_amdgcn_raw_buffer_load_b64(r_e0, (int)vo_e0[tp], so16_, 0)); \
-        const f16x4_ l_ = __builtin_bit_cast(f16x4_, __builtin_amdgcn_raw_buffer_load_b64(r_e0, (int)vo_e0[tp], so16_ + OHW * 16, 0)); \
-        _Pragma("unroll") for (int q = 0; q < 4; ++q) E[tp][q] = ((float)h_[q] + (float)l_[q]) * (1.0f / ASC16);  \
+        const u32x2_ h_ = __builtin_bit_cast(u32x2_, __builtin_amdgcn_raw_buffer_load_b64(r_e0, (int)vo_e0[tp], so16_, 0)); \
+        const u32x2_ l_ = __builtin_bit_cast(u32x2_, __builtin_amdgcn_raw_buffer_load_b64(r_e0, (int)vo_e0[tp], so16_ + OHW * 16, 0)); \
+        _Pragma("unroll") for (int q = 0; q < 4; ++q) E[tp][q] = s16_join(h_[q >> 1], l_[q >> 1], q & 1);         \
       }                                                                                                           \
     } else {                                                                                                      \
       _Pragma("unroll") for (int q = 0; q < 4; ++q) _Pragma("unroll") for (int tp = 0; tp < TP; ++tp)             \
@@ -180,15 +176,9 @@ __device__ __forceinline__ void conv_epilogue_lean_res(const accflow_conv_desc& 
         unsigned hi2[2], lo2[2];
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
-          const float a = o[tp][2 * k] * ASC16, b = o[tp][2 * k + 1] * ASC16;
-          bad16 |= !(fabsf(a) < 65520.0f) | !(fabsf(b) < 65520.0f);
-          const f32x2_ v2 = {a, b};
-          const f16x2_ hq = __builtin_convertvector(v2, f16x2_);
-          const f32x2_ back = __builtin_convertvector(hq, f32x2_);
-          const f32x2_ rest = {a - back[0], b - back[1]};
-          const f16x2_ lq = __builtin_convertvector(rest, f16x2_);
-          hi2[k] = __builtin_bit_cast(unsigned, hq);
-          lo2[k] = __builtin_bit_cast(unsigned, lq);
+          const float a = o[tp][2 * k] * S16_SCALE, b = o[tp][2 * k + 1] * S16_SCALE;
+          bad16 |= s16_bad2(a, b);
+          s16_split2(a, b, hi2[k], lo2[k]);
         }
         const u32x2_ hv = {hi2[0], hi2[1]}, lv = {lo2[0], lo2[1]};
         __builtin_amdgcn_raw_buffer_store_b64(hv, r_o16, (int)vo_16[tp], so16, 0);

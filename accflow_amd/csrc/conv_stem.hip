@@ -65,16 +65,13 @@ __global__ __launch_bounds__(256, ACCFLOW_STEM_WAVES) void conv_stem7_kernel(con
       v[it] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
                                             rsrci, ok ? (int)(((long long)c * d.H * d.W + (long long)iy * d.W + ix) * 4) : -1, 0, 0));
     }
-    constexpr float ASC0 = (float)(1 << ACCFLOW_F16_ASHIFT);
     bool bad0 = false;
 #pragma unroll
     for (int it = 0; it < NIT; ++it)
-      if (slot[it] >= 0) {      // split8_f16's arithmetic, one element: hi = fp16(x 2^4), lo = fp16(x 2^4 - hi)
-        const float a = v[it] * ASC0;
-        bad0 |= !(fabsf(a) < 65520.0f);
-        const _Float16 hq = (_Float16)a;
-        const _Float16 lq = (_Float16)(a - (float)hq);
-        P[slot[it]] = (unsigned)__builtin_bit_cast(unsigned short, hq) | ((unsigned)__builtin_bit_cast(unsigned short, lq) << 16);
+      if (slot[it] >= 0) {      // one element per word: hi in the low half, lo in the high half
+        const float a = v[it] * S16_SCALE;
+        bad0 |= s16_bad(a);
+        P[slot[it]] = s16_split1(a);
       }
     if (tid < 64) P[ST_PWORDS + tid] = 0u;
     if (bad0 && d.guard) atomicOr(d.guard, 1);

@@ -214,8 +214,6 @@ __global__ __launch_bounds__(256) void corr_lookup_alt_kernel(const float* __res
 #pragma unroll
       for (int i = 0; i < 2 * R + 1; ++i) o[(long long)(i * 9 + j) * P] = tap(i, j);
   } else {
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
     lu32x4* o16 = reinterpret_cast<lu32x4*>(out + (long long)b * out_bs) + pix;
     bool bad = false;
     for (int oct = wv; oct < 11; oct += 4) {
@@ -225,21 +223,10 @@ __global__ __launch_bounds__(256) void corr_lookup_alt_kernel(const float* __res
         const int n = oct * 8 + t;
         buf[t] = n < 81 ? tap(n % 9, n / 9) : 0.0f;
       }
-      unsigned h[4], l[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float a = buf[2 * k] * (float)(1 << ACCFLOW_F16_ASHIFT), c = buf[2 * k + 1] * (float)(1 << ACCFLOW_F16_ASHIFT);
-        bad |= !(fabsf(a) < 65520.0f) | !(fabsf(c) < 65520.0f);
-        const f2 v = {a, c};
-        const h2 hq = __builtin_convertvector(v, h2);
-        const f2 back = __builtin_convertvector(hq, f2);
-        const f2 rr = {a - back[0], c - back[1]};
-        const h2 lq = __builtin_convertvector(rr, h2);
-        h[k] = __builtin_bit_cast(unsigned, hq);
-        l[k] = __builtin_bit_cast(unsigned, lq);
-      }
-      o16[(long long)((lvl * 11 + oct) * 2 + 0) * P] = lu32x4{h[0], h[1], h[2], h[3]};
-      o16[(long long)((lvl * 11 + oct) * 2 + 1) * P] = lu32x4{l[0], l[1], l[2], l[3]};
+      lu32x4 hi, lo;
+      s16_split8(buf, hi, lo, bad);
+      o16[(long long)((lvl * 11 + oct) * 2 + 0) * P] = hi;
+      o16[(long long)((lvl * 11 + oct) * 2 + 1) * P] = lo;
     }
     if (bad && guard) atomicOr(guard, 1);
   }

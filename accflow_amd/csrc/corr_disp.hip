@@ -118,21 +118,13 @@ __global__ __launch_bounds__(64) void corr_lookup_disp_kernel(const float* __res
   float buf[8];
   bool bad = false;
   auto flush = [&](int oct, int count) {
-    typedef float f2 __attribute__((ext_vector_type(2)));
-    typedef _Float16 h2 __attribute__((ext_vector_type(2)));
     unsigned h[4], l[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const float a = (2 * k < count) ? buf[2 * k] * (float)(1 << ACCFLOW_F16_ASHIFT) : 0.0f;
-      const float c = (2 * k + 1 < count) ? buf[2 * k + 1] * (float)(1 << ACCFLOW_F16_ASHIFT) : 0.0f;
-      bad |= !(fabsf(a) < 65520.0f) | !(fabsf(c) < 65520.0f);
-      const f2 v = {a, c};
-      const h2 hq = __builtin_convertvector(v, h2);
-      const f2 back = __builtin_convertvector(hq, f2);
-      const f2 r = {a - back[0], c - back[1]};
-      const h2 lq = __builtin_convertvector(r, h2);
-      h[k] = __builtin_bit_cast(unsigned, hq);
-      l[k] = __builtin_bit_cast(unsigned, lq);
+      const float a = (2 * k < count) ? buf[2 * k] * S16_SCALE : 0.0f;
+      const float c = (2 * k + 1 < count) ? buf[2 * k + 1] * S16_SCALE : 0.0f;
+      bad |= s16_bad2(a, c);
+      s16_split2(a, c, h[k], l[k]);
     }
     if (active) {
       o16[(long long)((lvl * 11 + oct) * 2 + 0) * P] = lu32x4{h[0], h[1], h[2], h[3]};

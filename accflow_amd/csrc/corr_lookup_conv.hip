@@ -70,7 +70,7 @@ __device__ __forceinline__ void static_for(F&& f) { static_for_impl(std::make_in
 
 constexpr int NSUPER = 10, NSTEP = 21;
 
-// split8_f16 (conv_common.h) with the range check kept in the VECTOR domain: the largest |x * s| seen so far as an integer
+// s16_split8 (s16_format.h) with the range check kept in the VECTOR domain: the largest |x * s| seen so far as an integer
 // maximum over the sign-cleared bit patterns (NaN > inf > every finite value), tested once at the end of the kernel.  The
 // compare-per-value form leaves a 64-bit SGPR mask per compare; in this kernel's 2 000-instruction straight-line body the
 // scheduler let those pile up (85 SGPR spills into VGPR lanes).
@@ -80,13 +80,7 @@ __device__ __forceinline__ void split8_f16_mx(const float (&x)[8], u32x4 (&out)[
   for (int j = 0; j < 4; ++j) {
     const float a = x[2 * j] * s, b = x[2 * j + 1] * s;
     mx = max(mx, max(__builtin_bit_cast(unsigned, a) & 0x7FFFFFFFu, __builtin_bit_cast(unsigned, b) & 0x7FFFFFFFu));
-    const f32x2 v = {a, b};
-    const f16x2 h = __builtin_convertvector(v, f16x2);
-    const f32x2 back = __builtin_convertvector(h, f32x2);
-    const f32x2 r = {a - back[0], b - back[1]};
-    const f16x2 l = __builtin_convertvector(r, f16x2);
-    hi[j] = __builtin_bit_cast(unsigned, h);
-    lo[j] = __builtin_bit_cast(unsigned, l);
+    s16_split2(a, b, hi[j], lo[j]);
   }
   { u32x4 v4 = {hi[0], hi[1], hi[2], hi[3]}; out[0] = v4; }
   { u32x4 v4 = {lo[0], lo[1], lo[2], lo[3]}; out[1] = v4; }
@@ -113,7 +107,6 @@ __global__ __launch_bounds__(512, 4) void corr_lookup_convc1_ws_kernel(const lc1
   const int H8 = a.H8, W8 = a.W8, P = H8 * W8;
   const int b = blockIdx.y;
   const int pix0 = blockIdx.x * 64;
-  constexpr float ASC = (float)(1 << ACCFLOW_F16_ASHIFT);
 
   if (wave < 4) {
     // ================= lookup role: level `wave` of the 64 pixels, lane = pixel =================
@@ -181,7 +174,7 @@ __global__ __launch_bounds__(512, 4) void corr_lookup_convc1_ws_kernel(const lc1
         if constexpr ((n & 7) == 7) {
           constexpr int c = n >> 3;
           u32x4 terms[2];
-          split8_f16_mx(buf, terms, mx, ASC);
+          split8_f16_mx(buf, terms, mx, S16_SCALE);
           Bst[(((c & 1) * 4 + lvl) * 2 + 0) * 64 + lane] = terms[0];
           Bst[(((c & 1) * 4 + lvl) * 2 + 1) * 64 + lane] = terms[1];
           __syncthreads();   // barrier c: stage c & 1 is complete
@@ -191,10 +184,10 @@ __global__ __launch_bounds__(512, 4) void corr_lookup_convc1_ws_kernel(const lc1
     });
     Tail[lvl * 64 + lane] = buf[0];
     // the tail value's range check (the multiplying waves split it): |x * 2^4| as a bit pattern
-    mx = max(mx, __builtin_bit_cast(unsigned, buf[0] * ASC) & 0x7FFFFFFFu);
+    mx = max(mx, __builtin_bit_cast(unsigned, buf[0] * S16_SCALE) & 0x7FFFFFFFu);
     __syncthreads();         // barrier 10: Tail is complete
     LC1_STAMP(11);
-    if (!(mx < 0x477FF000u) && a.guard) atomicOr(a.guard, 1);   // 0x477FF000 = 65520.0f
+    if (!(mx < S16_LIMIT_BITS) && a.guard) atomicOr(a.guard, 1);
     LC1_STAMP(12);
     LC1_STAMPS_OUT();
     return;
@@ -276,7 +269,7 @@ __global__ __launch_bounds__(512, 4) void corr_lookup_convc1_ws_kernel(const lc1
 #pragma unroll
       for (int q = 4; q < 8; ++q) x[q] = 0.0f;
       u32x4 terms[2];
-      split8_f16_mx(x, terms, mxd, ASC);
+      split8_f16_mx(x, terms, mxd, S16_SCALE);
       Bf[0][tp] = __builtin_bit_cast(bf16x8, terms[0]);
       Bf[1][tp] = __builtin_bit_cast(bf16x8, terms[1]);
     }

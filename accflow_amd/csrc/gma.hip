@@ -339,7 +339,7 @@ extern "C" int accflow_gma_aggregate_s16(const void* attn16, const float* v, con
                                 as_stream(stream));
 }
 
-// GMA attention -> S16 (gma_attn_gemm_kernel, conv2d_direct.hip): q and k are packed as fp16 hi / lo of x * 2^ASHIFT (k
+// GMA attention -> S16 (gma_attn_gemm_kernel, gma_attn.hip): q and k are packed as fp16 hi / lo of x * 2^ASHIFT (k
 // carries GMA's scale dim_head^-1/2), two passes of the register-only GEMM per item.
 // ws: accflow_gma_attention_s16_ws_bytes(D, H, W) = two packs + partial / final column statistics.
 extern "C" long long accflow_gma_attention_s16_ws_bytes(int D, int H, int W) {

@@ -93,8 +93,6 @@ __global__ __launch_bounds__(256) void gma_alt_pack_v_kernel(const float* __rest
 // two waves per SIMD fit the register file)
 template <int NI, int KT>
 __global__ __launch_bounds__(256, 2) void gma_alt_aggregate_kernel(const gma_alt_args a) {
-  typedef float f32x2_ __attribute__((ext_vector_type(2)));
-  typedef _Float16 f16x2_ __attribute__((ext_vector_type(2)));
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, kh = lane >> 5, lh4 = kh * 4;
@@ -114,7 +112,7 @@ __global__ __launch_bounds__(256, 2) void gma_alt_aggregate_kernel(const gma_alt
                                               0, 2 * vterm_bytes, 0x00020000);
   const bool iok = i < a.P;
   const float m_i = iok ? a.stats[2 * i] : 0.0f;
-  const float inv_i = iok ? a.stats[2 * i + 1] * (float)(1 << ACCFLOW_F16_ASHIFT) : 0.0f;
+  const float inv_i = iok ? a.stats[2 * i + 1] * S16_SCALE : 0.0f;
   const int qvoff = (kh * a.Ppad + i) * 16;
   f32x16 out[NI][4];
 #pragma unroll
@@ -161,13 +159,7 @@ __global__ __launch_bounds__(256, 2) void gma_alt_aggregate_kernel(const gma_alt
           const int j = jg + 8 * (e2 >> 1) + lh4 + ((2 * e2) & 3);
           const float pa = j < a.P ? expf(acc[tc][r] * a.acc_scale - m_i) * inv_i : 0.0f;
           const float pb = j + 1 < a.P ? expf(acc[tc][r + 1] * a.acc_scale - m_i) * inv_i : 0.0f;
-          const f32x2_ v2 = {pa, pb};                             // values in [0, 16]
-          const f16x2_ hq = __builtin_convertvector(v2, f16x2_);
-          const f32x2_ back = __builtin_convertvector(hq, f32x2_);
-          const f32x2_ rest = {pa - back[0], pb - back[1]};
-          const f16x2_ lq = __builtin_convertvector(rest, f16x2_);
-          hi[e2] = __builtin_bit_cast(unsigned, hq);
-          lo[e2] = __builtin_bit_cast(unsigned, lq);
+          s16_split2(pa, pb, hi[e2], lo[e2]);                     // values in [0, 16]: no range check
         }
         const u32x4 hv = {hi[0], hi[1], hi[2], hi[3]}, lv = {lo[0], lo[1], lo[2], lo[3]};
         const bf16x8 ph = __builtin_bit_cast(bf16x8, hv), pl = __builtin_bit_cast(bf16x8, lv);

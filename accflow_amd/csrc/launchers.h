@@ -12,8 +12,9 @@ int accflow_launch_conv_f32(const accflow_conv_desc& d, int wc, int wp, int tc, 
 int accflow_launch_conv_bf16s(const accflow_conv_desc& d, int tc, int tp, int Z, hipStream_t st);          // conv2d_bf16s.hip
 int accflow_launch_corr_disp_bf16s(const accflow_conv_desc& d, hipStream_t st);
 int accflow_launch_conv_direct(const accflow_conv_desc& d, const conv_plan& p, hipStream_t st);            // conv2d_direct.hip
-int conv_ksplit_reduce_launch(const accflow_conv_desc& d, int Z, hipStream_t st);
-int accflow_launch_corr_disp_direct(const accflow_conv_desc& d, hipStream_t st);
+int conv_ksplit_reduce_launch(const accflow_conv_desc& d, int Z, hipStream_t st);                          // conv_ksplit.hip
+int accflow_launch_corr_disp_direct(const accflow_conv_desc& d, hipStream_t st);                           // corr_gemm.hip
+// gma_attn.hip
 int accflow_launch_gma_attn(const void* kpack, const void* qpack, float* part, float* stats, void* out16, float acc_scale, int P,
                             int D, int Ppad, hipStream_t st);
 int accflow_launch_gma_attn_stats(const void* kpack, const void* qpack, float* part, float* stats, float acc_scale, int P, int D,

@@ -375,9 +375,7 @@ __global__ __launch_bounds__(256) void instance_norm_apply_s16res_kernel(const f
     v[j] = 0.0f;
     if (c < C) {
       const long long plane = (long long)b * C + c, e = plane * HW + pix;
-      const _Float16 hh = __builtin_bit_cast(_Float16, (unsigned short)((hw[j >> 1] >> (16 * (j & 1))) & 0xFFFFu));
-      const _Float16 ll = __builtin_bit_cast(_Float16, (unsigned short)((lw[j >> 1] >> (16 * (j & 1))) & 0xFFFFu));
-      const float r = ((float)hh + (float)ll) * (1.0f / (float)(1 << ACCFLOW_F16_ASHIFT));
+      const float r = s16_join(hw[j >> 1], lw[j >> 1], j & 1);
       float t = fmaxf((x[e] - meanrstd[2 * plane]) * meanrstd[2 * plane + 1], 0.0f);
       t = fmaxf(r + t, 0.0f);
       if (out) out[e] = t;

@@ -3,7 +3,7 @@
 //   the fp16 row scale   wscale16 = 2^-(k + ACCFLOW_F16_ASHIFT), k such that the row maximum * 2^k lies in [2^10, 2^11);
 //   the term splits      three bf16 terms; fp16 hi + lo with a zero third slot; 8 values -> one 16-byte hi and lo chunk;
 //   the k-table entry    {channel inside its source, ky, kx, source}, padding entries never in range.
-// (split8_f16 / split8_bf16 of conv_common.h are the K-loop kernels' splits of ACTIVATIONS: vector converts, a range check.)
+// (s16_split8 of s16_format.h / split8_bf16 of conv_common.h are the K-loop kernels' splits of ACTIVATIONS: vector converts, a range check.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include "accflow_hip.h"

@@ -1,5 +1,5 @@
 """Every route of the all-pairs correlation volume and its 4-level pyramid (csrc/corr_volume.hip, corr_disp_gemm_kernel /
-corr_disp_ring_kernel / accflow_launch_corr_disp_direct in csrc/conv2d_direct.hip, corr_disp_store2 in csrc/conv_common.h,
+corr_disp_ring_kernel / accflow_launch_corr_disp_direct in csrc/corr_gemm.hip, corr_disp_store2 in csrc/conv_common.h,
 the pooling kernels of csrc/corr_volume.hip and csrc/corr_disp.hip) against a float64 reference written HERE:
 level 0 = f1^T f2 / sqrt(C), levels 1..3 = 2x2 means with floor sizes, pool of pool - plain torch on the CPU.
 
@@ -150,7 +150,7 @@ def test_route_table_is_the_one_in_the_sources():
     csrc = ("accflow_amd", "csrc")
     assert "#define ACCFLOW_F16_ASHIFT %d\n" % ASHIFT in src("include", "accflow_hip.h")
     assert "return (K + 31) / 32 * 32;" in src(*csrc, "conv_plan.cpp")
-    direct, vol, disp = src(*csrc, "conv2d_direct.hip"), src(*csrc, "corr_volume.hip"), src(*csrc, "corr_disp.hip")
+    direct, vol, disp = src(*csrc, "corr_gemm.hip"), src(*csrc, "corr_volume.hip"), src(*csrc, "corr_disp.hip")
     common, bf16s = src(*csrc, "conv_common.h"), src(*csrc, "conv2d_bf16s.hip")
     rows = {r: corr_route(*a)[3] for r, a in (("V5", ("disp", "bf16x6", 128, 8, 8)), ("V6", ("disp", "bf16x3", 128, 8, 8)),
                                               ("V7", ("disp", "f16x3", 128, 8, 8)))}

@@ -214,6 +214,8 @@ def test_host_thresholds_are_the_ones_restated_here():
     direct = src(*csrc, "conv2d_direct.hip")
     bf = src(*csrc, "conv2d_bf16s_kernel.h")
     moved = [src(*csrc, f) for f in ("conv_small.hip", "corr_volume.hip", "gma_alt.hip")]   # (what conv2d.hip held until the split)
+    corr_gemm = src(*csrc, "corr_gemm.hip")
+    moved += [src(*csrc, "conv_ksplit.hip"), corr_gemm, src(*csrc, "gma_attn.hip")]         # (... and conv2d_direct.hip until its own)
     for text in [conv, gma, pack, direct, bf, src(*csrc, "conv2d_s16m.hip")] + moved:       # ... and no launcher decides any of it again
         assert "fill > best" not in text and "< 320" not in text and "< 700" not in text and "getenv(\"ACCFLOW_DIRECT" not in text
     # the products the split kernels keep: a = weights, b = activations, terms (2,0) (0,2) (1,1) only with three terms
@@ -223,7 +225,7 @@ def test_host_thresholds_are_the_ones_restated_here():
                  "c = s_mfma<F16>(a[NT == 3 ? 1 : 1][tc], b[0][tp], c);", "c = s_mfma<F16>(a[0][tc], b[1][tp], c);",
                  "c = s_mfma<F16>(a[0][tc], b[0][tp], c);"):
         assert bf.count(line) == 1, line
-    assert "constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};" in direct
+    assert "constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};" in corr_gemm
 
 
 # ------------------------------------------------------------------------------------------------

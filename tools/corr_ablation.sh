@@ -9,7 +9,7 @@ if [ "${1:-build}" = build ]; then
     d=tools/bin/lib_cabl$m
     mkdir -p $d
     rm -rf $d/obj && cp -a accflow_amd/lib/obj $d/obj
-    python -m accflow_amd.build --libdir=$d --unit-define=conv2d_direct.hip:ACCFLOW_CORR_ABL=$m | tail -1
+    python -m accflow_amd.build --libdir=$d --unit-define=corr_gemm.hip:ACCFLOW_CORR_ABL=$m | tail -1
   done
 else
   for m in 0 $ABLS 0; do
