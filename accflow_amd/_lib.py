@@ -181,6 +181,12 @@ SIGNATURES = {
     "accflow_conv_wgrad_plan": [c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_ll, c_ll, ctypes.POINTER(c_i), c_i],
     "accflow_deform_conv_backward_f32": [c_f, c_ll, c_f, c_ll, c_f, c_ll, c_f, c_f, c_ll, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_i, c_i,
                                          c_i, c_f],
+    "accflow_gru_reset_forward_f32": [c_f, c_ll, c_f, c_ll, c_f, c_ll, c_i, c_ll, c_f],
+    "accflow_gru_update_forward_f32": [c_f, c_ll, c_f, c_ll, c_f, c_ll, c_f, c_ll, c_i, c_ll, c_f],
+    "accflow_gru_update_backward_f32": [c_f, c_ll, c_f, c_ll, c_f, c_ll, c_f, c_ll, c_f, c_ll, c_f, c_ll, c_f, c_ll, c_i, c_ll, c_f],
+    "accflow_gru_reset_backward_f32": [c_f, c_ll, c_f, c_ll, c_f, c_ll, c_f, c_ll, c_f, c_ll, c_i, c_ll, c_f],
+    "accflow_seq_l1_ws_bytes": [c_ll],
+    "accflow_seq_l1_f32": [c_f, c_f, c_f, c_ll, ctypes.c_double, c_f, c_f, c_f],
 }
 
 # the size queries: element / byte / word counts that may pass 2^31 come back as long long, everything else as int
@@ -190,6 +196,7 @@ RETURNS_LONGLONG = frozenset((
     "accflow_gma_attention_s16_ws_bytes", "accflow_gma_attention_alt_ws_bytes", "accflow_gma_aggregate_alt_ws_bytes",
     "accflow_corr_disp_level_elems", "accflow_corr_alt_pyramid_elems", "accflow_s16_item_words",
     "accflow_gma_attention_pos_ws_bytes", "accflow_flow_metrics_ws_bytes", "accflow_flow_maxrad_ws_bytes",
+    "accflow_seq_l1_ws_bytes",
 ))
 
 _lock = threading.Lock()

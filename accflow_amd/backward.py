@@ -10,6 +10,8 @@ blend and the convex upsampling only.  These wrappers are the gradients of exact
   conv_wgrad      weight / bias gradient (accflow_conv_wgrad_f32)
   act_backward    relu / sigmoid / tanh from the activation's output
   deform_conv_backward, blend_backward, convex_upsample_backward, l1_grad, add_
+  gru_reset_forward / gru_update_forward and their backward passes, seq_l1: the SepConvGRU gate products and one term of
+                  sequence_loss_raft for the update block's fine-tuning (train_raft.py; csrc/raft_train.hip)
 
 Parity is checked per operator against torch autograd of the same op in float64 (tests/test_backward.py) and end to end
 against the reference's own autograd through committed gradient fixtures (tests/golden/make_grad_golden.py)."""
@@ -52,6 +54,83 @@ def l1_grad(pred, gt, scale):
     out = torch.empty_like(pred)
     _check(lib.accflow_l1_grad_f32(_p(pred), _p(gt), _p(out), pred.numel(), float(scale), _stream()), "accflow_l1_grad_f32")
     return out
+
+
+def _planes(who, *named):
+    """Batch strides of same-shaped (B, C, H, W) operands (channel slices allowed) as the gate kernels take them."""
+    shape = tuple(named[0][0].shape)
+    out = []
+    for t, n in named:
+        if tuple(t.shape) != shape:
+            raise RuntimeError("%s: %s is %s, expected %s" % (who, n, tuple(t.shape), shape))
+        out.append(_plane4(t, n))
+    return out
+
+
+def _like(t):
+    return torch.empty(tuple(t.shape), dtype=torch.float32, device=t.device)
+
+
+def gru_reset_forward(r, h, out=None):
+    """rh = r * h (update.py:50); operands and `out` may be channel slices ((B, C, H, W) with a batch stride)."""
+    lib = _lib.load()
+    out = _like(h) if out is None else out
+    rb, hb, ob = _planes("gru_reset_forward", (r, "r"), (h, "h"), (out, "rh"))
+    _check(lib.accflow_gru_reset_forward_f32(_p(r), rb, _p(h), hb, _p(out), ob, h.shape[0], _chw(h), _stream()),
+           "accflow_gru_reset_forward_f32")
+    return out
+
+
+def gru_update_forward(z, h, q, out=None):
+    """h_new = (1 - z) * h + z * q (update.py:51); operands and `out` may be channel slices."""
+    lib = _lib.load()
+    out = _like(h) if out is None else out
+    zb, hb, qb, ob = _planes("gru_update_forward", (z, "z"), (h, "h"), (q, "q"), (out, "h_new"))
+    _check(lib.accflow_gru_update_forward_f32(_p(z), zb, _p(h), hb, _p(q), qb, _p(out), ob, h.shape[0], _chw(h), _stream()),
+           "accflow_gru_update_forward_f32")
+    return out
+
+
+def gru_update_backward(dh_new, z, h, q, daz=None, daq=None, dh=None):
+    """Backward of gru_update_forward with sigmoid' / tanh' folded in (z, q are the activations' OUTPUTS) ->
+    (daz = dh_new (q - h) z (1 - z), daq = dh_new z (1 - q^2), dh = dh_new (1 - z)); the outputs may be channel slices."""
+    lib = _lib.load()
+    daz, daq, dh = (_like(h) if t is None else t for t in (daz, daq, dh))
+    gb, zb, hb, qb, azb, aqb, dhb = _planes("gru_update_backward", (dh_new, "dh_new"), (z, "z"), (h, "h"), (q, "q"),
+                                            (daz, "daz"), (daq, "daq"), (dh, "dh"))
+    _check(lib.accflow_gru_update_backward_f32(_p(dh_new), gb, _p(z), zb, _p(h), hb, _p(q), qb, _p(daz), azb, _p(daq), aqb,
+                                               _p(dh), dhb, h.shape[0], _chw(h), _stream()), "accflow_gru_update_backward_f32")
+    return daz, daq, dh
+
+
+def gru_reset_backward(drh, r, h, dh, dar=None):
+    """Backward of gru_reset_forward with sigmoid' folded in -> dar = drh h r (1 - r); dh += drh r in place."""
+    lib = _lib.load()
+    dar = _like(h) if dar is None else dar
+    gb, rb, hb, arb, dhb = _planes("gru_reset_backward", (drh, "drh"), (r, "r"), (h, "h"), (dar, "dar"), (dh, "dh"))
+    _check(lib.accflow_gru_reset_backward_f32(_p(drh), gb, _p(r), rb, _p(h), hb, _p(dar), arb, _p(dh), dhb, h.shape[0], _chw(h),
+                                              _stream()), "accflow_gru_reset_backward_f32")
+    return dar
+
+
+def seq_l1(pred, gt, weight, loss_out, dpred=None):
+    """One term of sequence_loss_raft (loss.py:10-13): loss_out (1-element float64 device tensor) += weight * mean |pred - gt|
+    from a fixed-order reduction (bit-reproducible, never on the host) -> dpred = weight / numel * sign(pred - gt)."""
+    lib = _lib.load()
+    pred, gt = ops._dense(pred, "pred"), ops._dense(gt, "gt")
+    if tuple(pred.shape) != tuple(gt.shape):
+        raise RuntimeError("seq_l1: pred %s and gt %s differ" % (tuple(pred.shape), tuple(gt.shape)))
+    if not (loss_out.is_cuda and loss_out.dtype == torch.float64 and loss_out.numel() == 1):
+        raise RuntimeError("seq_l1: loss_out is a 1-element float64 CUDA tensor")
+    dpred = torch.empty_like(pred) if dpred is None else ops._dense(dpred, "dpred")
+    n = pred.numel()
+    nbytes = lib.accflow_seq_l1_ws_bytes(n)
+    if nbytes <= 0 or dpred.numel() != n:
+        raise RuntimeError("seq_l1: %d elements refused" % n)
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=pred.device)
+    _check(lib.accflow_seq_l1_f32(_p(pred), _p(gt), _p(dpred), n, float(weight), _p(loss_out), _p(ws), _stream()),
+           "accflow_seq_l1_f32")
+    return dpred
 
 
 def blend_backward(dy, f1, f2, m):

@@ -21,7 +21,7 @@ SOURCES = ["conv2d_f32.hip", "conv2d_f32_v1.hip", "conv2d_f32_v2.hip", "conv2d_f
            "conv2d_direct_v_bf16x6.hip", "conv2d_direct_v_bf16n.hip", "conv2d_direct_v_f16.hip", "conv2d_direct_v_s16.hip", "conv2d_direct_v_s16tg.hip", "conv2d_direct_v_s16k.hip", "conv2d_direct_v_s16k9.hip",
            "conv2d_direct_v_f16n.hip", "conv2d_direct_v_bf16x3.hip", "conv_s16m_v0.hip", "conv_s16m_v1.hip", "conv_s16m_v2.hip",
            "conv_s16m_v3.hip", "conv2d_s16m.hip", "conv_stem.hip", "conv2d_direct.hip", "conv_ksplit.hip", "corr_gemm.hip", "gma_attn.hip", "conv_pack.hip", "conv_small.hip", "conv2d.hip", "conv_plan.cpp", "corr_volume.hip",
-           "corr_lookup.hip", "corr_disp.hip", "corr_alt.hip", "corr_lookup_conv.hip", "sampling.hip", "flow_metrics.hip", "flow_viz.hip", "frame_io.hip", "forward_interp.hip", "misc.hip", "gma.hip", "gma_alt.hip", "gma_pos.hip", "backward.hip"]
+           "corr_lookup.hip", "corr_disp.hip", "corr_alt.hip", "corr_lookup_conv.hip", "sampling.hip", "flow_metrics.hip", "flow_viz.hip", "frame_io.hip", "forward_interp.hip", "misc.hip", "gma.hip", "gma_alt.hip", "gma_pos.hip", "backward.hip", "raft_train.hip"]
 ARCH = "gfx950"
 
 

@@ -785,6 +785,32 @@ int accflow_deform_conv_backward_f32(const float* x, long long x_bs, const float
                                      long long dmask_bs, const float* dcols, float* dx, long long dx_bs, float* doffset,
                                      float* ddmask, int B, int C, int H, int W, int KH, int KW, int padH, int padW, void* stream);
 
+/* ---- Fine-tuning RAFT's update block through the refinement loop (fine_tune.py:203-243, loss.py:4-25; the encoders frozen,
+ * coords1 detached per iteration, raft.py:128): what that graph needs beyond the kernels above - the SepConvGRU gate products
+ * (update.py:45-60) with their backward passes, and one term of sequence_loss_raft.  Elementwise over (B, CHW) fp32 planes,
+ * every operand with its own batch stride (channel slices of the [h | x], [r*h | x], [z | r] buffers; 1 <= B <= 65535); 16-byte
+ * accesses when CHW is a multiple of 4.  Vector stores only, no atomics. ---- */
+/* rh = r h */
+int accflow_gru_reset_forward_f32(const float* r, long long r_bs, const float* h, long long h_bs, float* rh, long long rh_bs, int B,
+                                  long long CHW, void* stream);
+/* h_new = (1 - z) h + z q */
+int accflow_gru_update_forward_f32(const float* z, long long z_bs, const float* h, long long h_bs, const float* q, long long q_bs,
+                                   float* h_new, long long hn_bs, int B, long long CHW, void* stream);
+/* from dh_new and the activations' outputs z = sigmoid(az), q = tanh(aq): daz = dh_new (q - h) z (1 - z), daq = dh_new z (1 - q^2),
+ * dh = dh_new (1 - z) (written) - the pre-activation gradients, no separate activation backward */
+int accflow_gru_update_backward_f32(const float* dh_new, long long dhn_bs, const float* z, long long z_bs, const float* h,
+                                    long long h_bs, const float* q, long long q_bs, float* daz, long long daz_bs, float* daq,
+                                    long long daq_bs, float* dh, long long dh_bs, int B, long long CHW, void* stream);
+/* from drh and r = sigmoid(ar): dar = drh h r (1 - r) (written), dh += drh r (accumulated) */
+int accflow_gru_reset_backward_f32(const float* drh, long long drh_bs, const float* r, long long r_bs, const float* h, long long h_bs,
+                                   float* dar, long long dar_bs, float* dh, long long dh_bs, int B, long long CHW, void* stream);
+/* One term of sequence_loss_raft (loss.py:10-13) on contiguous pred / gt of n elements: dpred = (float)(weight / n) sign(pred - gt)
+ * (0 at equality) and loss[0] += weight * sum |pred - gt| / n (double, device) from a fixed-order two-stage reduction: the value is
+ * bit-reproducible and stays on the device.  ws: accflow_seq_l1_ws_bytes(n) bytes of scratch, 8-byte aligned (0: n refused). */
+long long accflow_seq_l1_ws_bytes(long long n);
+int accflow_seq_l1_f32(const float* pred, const float* gt, float* dpred, long long n, double weight, double* loss, void* ws,
+                       void* stream);
+
 int accflow_abi_version(void);
 /* sizeof(accflow_conv_desc) / sizeof(accflow_conv_src) as this library was compiled: a binding compares them with its own mirror
  * of the structures at load time (accflow_amd/_lib.py does), so that a field added on one side only fails loudly. */
